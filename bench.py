@@ -10,6 +10,11 @@ local batch 4 (forward + loss + backward, SDXL-base UNet, 1024^2 => latents 4x12
 then gradient reduce-scatter, global-norm clip, Raven AdamW (m/v resident in HBM) and parameter
 all-gather.  Global batch is fixed => "scaling": "strong".  Synthetic cached latents / embeddings and
 seed-generated weights (no network: no dataset, no SDXL checkpoint).  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set-up, `--warmup` iterations, `--steps` timed iterations, the outputs
+of the last one if `--dump-outputs DIR` is given, the JSON line.  `--full` adds everything else the line can carry: the exchange
+anatomy of the timed iterations, the per-kernel roofline (an eagerly profiled micro-step, live rocprofv3 --pmc child passes),
+the same workload through trainer.train, the other BASELINE configurations and local batches, and the CPU baseline.
 """
 import argparse
 import json
@@ -471,28 +476,82 @@ def hbm_roofline(breakdown):
     return out
 
 
+DUMP_SAMPLE = 1 << 22         # parameter / moment elements written by --dump-outputs (3 x 16 MiB in float32)
+DUMP_SEED = 1234
+
+
+def dump_outputs(out_dir, unet, opt, loss, gn, world):
+    """What the timed path computed in its last iteration, as float32 .npy files in `out_dir`: the loss of its last micro-step
+    (loss.npy: the step's loss buffer holds one micro-step at a time, as last_loss), the global gradient norm before clipping (grad_norm.npy), and at DUMP_SAMPLE fixed positions of the model --
+    drawn with seed DUMP_SEED, uniformly over the parameter elements, sorted by offset in the flat parameter buffer -- the updated
+    parameters (params_sample.npy) and, at one rank (they are sharded across ranks otherwise), Raven's first and second moments
+    at the same positions (exp_avg_sample.npy, exp_avg_sq_sample.npy)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    starts, sizes = [], []
+    for o, st, _ in unet._slots.values():
+        starts.append(o)
+        sizes.append(math.prod(st))
+    starts, sizes = torch.tensor(starts, dtype=torch.int64), torch.tensor(sizes, dtype=torch.int64)
+    ends = torch.cumsum(sizes, 0)
+    total = int(ends[-1])
+    if total <= DUMP_SAMPLE:
+        pick = torch.arange(total, dtype=torch.int64)
+    else:
+        pick = torch.randint(total, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(DUMP_SEED), dtype=torch.int64)
+    j = torch.searchsorted(ends, pick, right=True)
+    flat = (starts[j] + pick - (ends[j] - sizes[j])).sort().values
+    unet.wait_tail_params()
+    opt.synchronize_state()
+    torch.cuda.synchronize()
+    arrays = {"loss": loss.detach().float().reshape(1).cpu(),
+              "grad_norm": gn.detach().float().reshape(1).cpu(),
+              "params_sample": unet.pflat[flat.to(unet.device)].float().cpu()}
+    if world == 1:
+        ra, rb, roff = [], [], []
+        for rs, offs in zip(opt.ranges, opt.range_off):
+            for (a_, b_), o_ in zip(rs, offs):
+                ra.append(a_); rb.append(b_); roff.append(o_)
+        ra, rb, roff = (torch.tensor(v, dtype=torch.int64) for v in (ra, rb, roff))
+        k = torch.searchsorted(ra, flat, right=True) - 1
+        if bool((k < 0).any()) or bool((flat >= rb[k.clamp(min=0)]).any()):
+            raise RuntimeError("--dump-outputs: a sampled parameter element has no optimizer state")
+        midx = roff[k] + flat - ra[k]
+        for name, src in (("exp_avg_sample", opt.m_host if opt.state_on_host else opt.m_dev),
+                          ("exp_avg_sq_sample", opt.v_host if opt.state_on_host else opt.v_dev)):
+            arrays[name] = src[midx.to(src.device)].float().cpu()
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also collect the exchange anatomy, the per-kernel roofline (with live rocprofv3 "
+                         "--pmc passes), the trainer.train leg, the other configurations / local batches and the CPU baseline; "
+                         "without it none of these run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed iteration computed to DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--graph", action="store_true", help="replay a captured hipGraph per micro-step instead of eager multi-stream issue")
-    ap.add_argument("--profile-out", default=None, help="write the per-op-class event breakdown here (json)")
+    ap.add_argument("--profile-out", default=None, help="with --full: write the per-op-class event breakdown here (json)")
     ap.add_argument("--local-batch", type=int, default=LOCAL_BATCH,
                     help="samples per micro-step and GPU (BASELINE configs[1] = 4; larger values are an experiment: same global batch, fewer micro-steps)")
     ap.add_argument("--serial", action="store_true", help="issue everything on one stream (for profiles whose per-kernel durations are uncontended)")
     ap.add_argument("--double-buffer", action="store_true", help="experiment: two activation pools, deferred weight-gradient join")
     ap.add_argument("--through-trainer", type=int, default=5, metavar="ITERS",
-                    help="also time ITERS iterations of the same workload through trainer.train (on-disk cache, DataLoader, reporter); 0 = skip")
-    ap.add_argument("--no-live-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes (traffic / MFMA-busy of the dominant class)")
+                    help="with --full: also time ITERS iterations of the same workload through trainer.train (on-disk cache, DataLoader, reporter); 0 = skip")
+    ap.add_argument("--no-live-pmc", action="store_true", help="with --full: skip the rocprofv3 --pmc child passes (traffic / MFMA-busy of the dominant class)")
     ap.add_argument("--trainer-child", type=int, default=0, help=argparse.SUPPRESS)     # internal: the --through-trainer leg in its own process
     ap.add_argument("--config", default="cfg2", choices=sorted(LEGS),
                     help="cfg2 (default) = the headline line; any other name times THAT workload alone on one GPU and prints {'leg': ...}")
     ap.add_argument("--leg", default=None, choices=sorted(LEGS), help=argparse.SUPPRESS)   # internal: one secondary leg in its own process
     ap.add_argument("--leg-iters", type=int, default=3, help="timed iterations per secondary leg (after 2 warm-ups)")
     ap.add_argument("--other-configs", default="all", choices=["all", "none"],
-                    help="after the headline measurement (N = 1): also time cfg3 / cfg4 / cfg5 (host and device Titan) and local batches 8 / 16, "
+                    help="with --full, after the headline measurement (N = 1): also time cfg3 / cfg4 / cfg5 (host and device Titan) and local batches 8 / 16, "
                          "each in a child process, reported under 'other_configs' / 'local_batch_sweep'")
     ap.add_argument("--state-on-host", action="store_true", help="A/B: the reference's residency of the Raven moments (pinned host memory, streamed "
                     "per optimizer step) for the headline run; the line then says so in config.workload")
@@ -501,6 +560,10 @@ def main():
                     help="N>1 rehearsal on a box with ONE GPU: all ranks share cuda:0 and exchange through gloo (exercises the "
                          "data-parallel control flow of this script; the production backend is nccl = RCCL)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.profile_out and not a.full:
+        ap.error("--profile-out is written by the per-kernel profile of --full")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:      # started bare: be the launcher (no GPU call has been made in this process)
         raise SystemExit(spawn_ranks(a.gpus, sys.argv[1:]))
@@ -603,7 +666,8 @@ def main():
 
     for _ in range(a.warmup):
         iteration()
-    opt.enable_timing()
+    if a.full:
+        opt.enable_timing()
     barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
@@ -615,19 +679,23 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = tmax.item()
     loss_v, gn_v = float(loss.item()), float(gn.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, unet, opt, loss, gn, world)
     # exchange anatomy of the timed iterations, per rank (events on the streams the pieces ran on): optimizer boundary as the
     # main stream saw it (what is NOT hidden), per-region collective times / rates, m / v host-link copies
-    exch = opt.timing_summary()
-    opt.enable_timing(False)
-    exch = dict(exch or {}, host_placement=placement)
-    exch_all = [exch]
-    if world > 1:
-        exch_all = [None] * world
-        dist.all_gather_object(exch_all, exch)
+    exch_all = None
+    if a.full:
+        exch = opt.timing_summary()
+        opt.enable_timing(False)
+        exch = dict(exch or {}, host_placement=placement)
+        exch_all = [exch]
+        if world > 1:
+            exch_all = [None] * world
+            dist.all_gather_object(exch_all, exch)
 
     # ---- per-kernel roofline: one eager micro-step bracketed launch-by-launch with HIP events ----
     roof, breakdown = None, None
-    if rank == 0:
+    if rank == 0 and a.full:
         ops.PROFILER = ops.Profiler()
         unet.concurrent_wgrad = False        # serialise the two backward branches so per-launch durations are uncontended
         prof_step = TrainStep(unet, mode="epsilon", grad_accum=ga, world_size=world, use_graph=False)
@@ -672,8 +740,8 @@ def main():
 
     # ---- the same workload through trainer.train (the loop a user runs) -------------------------------------------------
     trainer_its = None
-    run_trainer = a.through_trainer > 0 and not a.graph and not a.rehearse_gloo and world == 1
-    run_others = world == 1 and a.other_configs == "all" and not a.graph and not a.rehearse_gloo
+    run_trainer = a.full and a.through_trainer > 0 and not a.graph and not a.rehearse_gloo and world == 1
+    run_others = a.full and world == 1 and a.other_configs == "all" and not a.graph and not a.rehearse_gloo
     if run_trainer or run_others:
         opt.synchronize_state()
         del opt, step, batches, unet          # give the device memory back: every child builds its own model
@@ -693,7 +761,7 @@ def main():
         others = other_configs(["cfg3", "cfg4", "cfg5_titan_device", "cfg5_titan_host", "cfg2_state_on_host", "lb8", "lb16"], a.leg_iters, a.other_budget)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         try:
             cpu = cpu_baseline(min(len(os.sched_getaffinity(0)), 64))
         except Exception as e:   # the baseline is reported beside the measurement; never fail the bench on it
@@ -708,7 +776,7 @@ def main():
             "config": {"workload": "SDXL-base UNet (2.567B params), epsilon pred, 1024x1024 (latent 4x128x128), ctx 77x2048, "
                                    f"local batch {lb} x grad-accum {ga} x {world} GPU = global batch 32, Raven AdamW (" + ("bf16 m/v in pinned host memory, streamed per step (--state-on-host)" if a.state_on_host else
                                    "bf16 m/v resident in HBM -- 10.3 GB of 288; the reference parks them in pinned host memory to fit 24 GB cards: "
-                                   "other_configs.cfg2_state_on_host --") + ", sharded 1/N per rank), clip 1.0, " + ("hipGraph replay" if a.graph else "eager 2-stream issue (dgrad chain || wgrad branch)"),
+                                   "other_configs.cfg2_state_on_host of --full --") + ", sharded 1/N per rank), clip 1.0, " + ("hipGraph replay" if a.graph else "eager 2-stream issue (dgrad chain || wgrad branch)"),
                        "global_batch": GLOBAL_BATCH, "parallelism": f"dp{world}"},
             "model_tflops_per_gpu": TRAIN_TFLOP_PER_SAMPLE * GLOBAL_BATCH / world * its,
             "mfma_roofline_frac_whole_step": TRAIN_TFLOP_PER_SAMPLE * GLOBAL_BATCH / world * its / PEAK_BF16_TFLOPS,
@@ -723,7 +791,7 @@ def main():
                 micro_step_ms=trainer_its.get("micro_step_ms") if isinstance(trainer_its, dict) and its and trainer_its["iters_per_sec"] < 0.97 * its else None,
                 what=f"trainer.train on the same workload (synthetic on-disk cache -> DataLoader -> micro-steps -> clip -> Raven -> "
                      f"reporter, loss read back per micro-step with a lag of two), median of {a.through_trainer} optimizer steps (the first two and the last of {a.through_trainer + 3} discarded)"),
-            "exchange": dict(per_rank=exch_all, note="mean ms per optimizer step over the timed iterations, HIP events on the stream each "
+            "exchange": None if exch_all is None else dict(per_rank=exch_all, note="mean ms per optimizer step over the timed iterations, HIP events on the stream each "
                              "piece ran on: optimizer_boundary_on_main_stream = what the step adds to the main stream (not hidden); "
                              "reduce_scatter / all_gather per region with their GB/s (payload bytes of the region / time); mv_h2d / mv_d2h (only with "
                              "state_on_host) = the owned shard of the pinned host Raven state over the host link"),

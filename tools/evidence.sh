@@ -5,7 +5,7 @@
 set -euo pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; O=$R/gpurun_out; TAG=${EVID_TAG:-r05}; mkdir -p "$O"
 cd /tmp; export TMPDIR=/tmp
-timeout -k 10 900 python3 $R/bench.py --steps 10 --warmup 2 --profile-out $O/${TAG}_event_breakdown.json > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err || { echo "bench failed"; tail -5 $O/${TAG}_bench.err; exit 1; }
+timeout -k 10 900 python3 $R/bench.py --steps 10 --warmup 2 --full --profile-out $O/${TAG}_event_breakdown.json > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err || { echo "bench failed"; tail -5 $O/${TAG}_bench.err; exit 1; }
 echo "bench done"; head -c 600 $O/${TAG}_bench_line.json; echo
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG} -o stats -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-live-pmc --through-trainer 0 > $O/prof_${TAG}.log 2>&1 || { echo "stats failed"; tail -5 $O/prof_${TAG}.log; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG}_serial -o stats -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-live-pmc --through-trainer 0 --serial > $O/prof_${TAG}_serial.log 2>&1 || { echo "serial stats failed"; tail -5 $O/prof_${TAG}_serial.log; exit 1; }
