@@ -1,4 +1,5 @@
 from .raven import RavenAdamW
 from .titan import TitanAdamW
+from .adamw8bit import PagedAdamW8bit
 
-__all__ = ["RavenAdamW", "TitanAdamW"]
+__all__ = ["RavenAdamW", "TitanAdamW", "PagedAdamW8bit"]

@@ -1,5 +1,5 @@
 """The training loop around the HIP step (train.py:2544-2830 restated on this package's objects): data feed -> micro-step
-(TrainStep: noise mix, UNet forward, weighted MSE, backward) -> clip -> Raven / Titan -> LR curve -> reporter ->
+(TrainStep: noise mix, UNet forward, weighted MSE, backward) -> clip -> Raven / Titan / 8-bit AdamW -> LR curve -> reporter ->
 checkpoints / resume.  It is the caller of the hot path (SURVEY.md 8a row a1 with the 8f rows plugged in); no GUI, no
 offline caching -- `config` is any object with the reference's flat attribute names (config.TrainingConfig builds one from
 a GUI preset: `python -m aozora_sdxl_training_amd.trainer --config X.json`, see main()).
@@ -21,13 +21,15 @@ import torch
 from . import checkpoint as ckpt
 from . import data as feed
 from .clip import clip_grad_norm_
-from .optimizers import RavenAdamW, TitanAdamW
+from .optimizers import PagedAdamW8bit, RavenAdamW, TitanAdamW
 from .schedule import (CustomCurveLRScheduler, TimestepSampler, ddpm_alphas_cumprod, generate_noise, make_time_ids,
                        seeded_torch_generator, timestep_loss_curve_from_config, trainable_mask)
 from .telemetry import Reporter
 from .train_step import TrainStep
 
 _RAVEN_DEFAULTS = dict(betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, debias_strength=0.3, momentum_dtype="bfloat16")
+_ADAMW8_DEFAULTS = dict(betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)      # config.py PAGED_ADAMW_8BIT_PARAMS
+_ADAMW8_DP_REFUSAL = "paged_adamw_8bit runs at one rank only: data-parallel training supports raven and titan"
 
 
 def _momentum_dtype(v):
@@ -62,6 +64,14 @@ def _optimizer(config, params):
                debias_strength=hp["debias_strength"], momentum_dtype=mdt)
 
 
+def _optimizer_8bit(config, params):
+    """create_optimizer (train.py:2271-2288): PagedAdamW8bit from PAGED_ADAMW_8BIT_PARAMS at lr = max(curve), min_8bit_size 4096."""
+    curve = getattr(config, "LR_CUSTOM_CURVE", [])
+    lr = max(p[1] for p in curve) if curve else config.LEARNING_RATE
+    hp = {**_ADAMW8_DEFAULTS, **dict(getattr(config, "PAGED_ADAMW_8BIT_PARAMS", {}) or {})}
+    return PagedAdamW8bit(params, lr=lr, betas=tuple(hp["betas"]), eps=hp["eps"], weight_decay=hp["weight_decay"], min_8bit_size=4096)
+
+
 def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = None, num_workers: Optional[int] = None):
     """Run config.MAX_TRAIN_STEPS micro-steps.  Returns dict(losses, grad_norms, lrs, micro_step, optimizer_step, saved).
 
@@ -72,6 +82,9 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     import torch.distributed as tdist
     dp = tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1
     world, rank = (tdist.get_world_size(), tdist.get_rank()) if dp else (1, 0)
+    eightbit = str(getattr(config, "OPTIMIZER_TYPE", "raven")).lower() == "paged_adamw_8bit"
+    if eightbit and dp:
+        raise ValueError(_ADAMW8_DP_REFUSAL)
     GA = int(config.GRADIENT_ACCUMULATION_STEPS)
     mode = getattr(config, "PREDICTION_TYPE", "epsilon")
     config.is_rectified_flow = (mode == "rectified_flow")
@@ -105,7 +118,10 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     # host link after every micro-step).  Measured at 1024^2, B = 4 x GA 8 (bench.py other_configs, round 5): 2 991 ms per iteration
     # with host gradients against 957 ms -- the host buffer exists for 12 GB cards, this one has 288 GB.
     host_titan = titan and not dp and bool(getattr(config, "TITAN_HOST_GRADIENTS", False))
-    if not host_titan:
+    if eightbit:
+        # one rank, the module-optimizer branch of the loop: expose_grads -> clip_grad_norm_ -> step (blockwise 8-bit AdamW in HIP)
+        optimizer = _optimizer_8bit(config, params)
+    elif not host_titan:
         # The flat fused optimizer (one rank: no collectives): m / v resident in HBM (or, RAVEN_STATE_ON_HOST, prefetched under the
         # window's last micro-step and written back under the next window), update of the whole flat range in one launch per
         # contiguous trainable range -- the same arithmetic as optimizers.RavenAdamW (which remains the drop-in class for foreign
@@ -389,7 +405,7 @@ def main(argv=None) -> int:
     (gui.py:5930-5975), here for the native step.  One process per GPU: started by torch.distributed.run (RANK / WORLD_SIZE /
     LOCAL_RANK in the environment) the ranks form an RCCL group and config.BATCH_SIZE is the GLOBAL micro-batch.
     Out of scope, refused with a message instead of being attempted: the Anima DiT mode, offline VAE / text-encoder caching
-    (the cache must exist), fp16 mixed precision and paged_adamw_8bit."""
+    (the cache must exist), fp16 mixed precision and paged_adamw_8bit under data parallel."""
     import os
     import sys
     from .config import TrainingConfig
@@ -400,8 +416,11 @@ def main(argv=None) -> int:
     if config.MIXED_PRECISION != "bfloat16":
         print(f"ERROR: MIXED_PRECISION={config.MIXED_PRECISION!r}: the HIP step computes in bf16 only.")
         return 2
-    if str(config.OPTIMIZER_TYPE).lower() not in ("raven", "titan"):
+    if str(config.OPTIMIZER_TYPE).lower() not in ("raven", "titan", "paged_adamw_8bit"):
         raise ValueError(f"Unsupported optimizer type: '{config.OPTIMIZER_TYPE}'")          # train.py:2290
+    if str(config.OPTIMIZER_TYPE).lower() == "paged_adamw_8bit" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        print(f"ERROR: {_ADAMW8_DP_REFUSAL}.")
+        return 2
     if config.SEED:
         set_seed(config.SEED)
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -371,6 +371,16 @@ int az_stage_inputs(int nseg, const void* src_ptrs, const void* dst_ptrs, const 
 /* Titan: offload grad range to host fp32 (copy, or add when accumulate) via device staging */
 /* ref: titan.py:93-100, 119-131 (post-accumulate hook: copy_ on the first micro-step, add_ afterwards) */
 int az_titan_offload(long n, const void* g, void* g_host_f32, void* staging_f32, int accumulate, void* stream);
+/* paged_adamw_8bit: one blockwise 8-bit AdamW step over ntensors bf16 tensors in one launch.
+ * desc (device): ntensors records of 12 int64 words -- p, g (storage pointers), state1, state2 (uint8 codes, or fp32 moments),
+ * absmax1, absmax2 (fp32 per 256-element block, 8-bit path), numel, first global block, flags (1 = 8-bit state, 2 = 4-D weight
+ * stored (O, kh, kw, I_pad) and read as (O, I, kh, kw), 4 = plain with 8-byte aligned p / g and 4-byte aligned codes), kh*kw
+ * (<= 32), I | I_pad << 32, hyper row -- then ntensors + 1 int64 first-block indices (the last = nblocks).  State is in LOGICAL
+ * element order; numel < 2^31.  hyper (device fp32 [rows][8]): b1, b2, 1-b1, 1-b2, step_size, eps*sqrt(1-b2^t), 1-lr*wd, wd>0.
+ * qmaps (device fp32 [2][256]): signed map of state1, unsigned map of state2.  coef (device fp32[1], may be null): g = bf16(g*coef). */
+/* ref: train.py:2271-2288 (create_optimizer: bnb.optim.PagedAdamW8bit) */
+int az_adamw8bit_step(int ntensors, const void* desc, long nblocks, const void* hyper, const void* qmaps, const void* coef,
+                      void* stream);
 
 /* ---- native launch tape: the executor seam (SURVEY.md 8b "az_unet_step") ----------------------------------------------------
  * The step's launch sequence is static (same entry points, pointers, streams and events every step of a resolution bucket).  The
