@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-from typing import Dict, List, Tuple
+from typing import Callable, Dict, List, NamedTuple, Tuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
@@ -45,6 +45,28 @@ class AozoraError(RuntimeError):
     pass
 
 
+# The operations of a launch tape (tape.py), one kind each.  Events and streams travel as objects (ForkEvent / torch.cuda.Event,
+# torch.cuda.Stream), not as raw handles: the Python replay issues torch events through torch, and a tape keeps them alive.
+class Call(NamedTuple):         # an entry point of the C ABI
+    name: str
+    args: tuple
+
+
+class Record(NamedTuple):       # event.record(stream)
+    event: object
+    stream: object
+
+
+class Wait(NamedTuple):         # event.wait(stream): the stream waits for the event
+    stream: object
+    event: object
+
+
+class Live(NamedTuple):         # host logic that depends on run-time state: fn(*args) runs in the caller at every replay
+    fn: Callable
+    args: tuple
+
+
 class _Lib:
     def __init__(self):
         if not os.path.exists(LIB_PATH):
@@ -59,8 +81,8 @@ class _Lib:
             fn.restype = _CTYPES[ret]
             fn.argtypes = [_CTYPES[t] for t, _ in args]
             self._fn[name] = fn
-        # Host launch tape (train_step.TrainStep): while `recorder` is a list every ABI call is appended to it as
-        # (bound C function, argument tuple).  The executor's launch sequence is static -- same entry points, same
+        # Host launch tape (train_step.TrainStep): while `recorder` is a list every ABI call is appended to it as a
+        # Call(entry-point name, argument tuple).  The executor's launch sequence is static -- same entry points, same
         # pointers, same streams every step -- so later steps re-issue the tape directly and skip the Python that
         # derived the arguments (operand checks, view arithmetic, tape of closures): ~25 us -> ~3 us of host time per
         # launch, which otherwise throttles the GPU where kernels are short.
@@ -72,7 +94,7 @@ class _Lib:
         if rc != 0:
             raise AozoraError(f"{name} failed with code {rc}" + (" (argument error)" if rc <= -1000 else " (HIP error)"))
         if self.recorder is not None:
-            self.recorder.append((fn, args))
+            self.recorder.append(Call(name, args))
         return rc
 
     def raw(self, name: str):
@@ -98,8 +120,9 @@ def get_option(name: str) -> int:
 class ForkEvent:
     """A fork / join event of the two-stream executor (include/aozora_hip.h az_event_create_fork): orders kernels of one device,
     is never timed or read by the host, and is created without the system-scope fence torch.cuda.Event records with -- half the
-    cost to the recording stream.  `cuda_event` / record() mirror torch.cuda.Event so that launch tapes treat both alike;
-    wait_on(stream) is stream.wait_event(event).  The calls bypass _Lib.call: the executor puts them on a recording tape itself."""
+    cost to the recording stream.  `cuda_event`, record(stream) and wait(stream) mirror torch.cuda.Event so that launch tapes
+    treat both alike (wait_on is an older name of wait).  The calls bypass _Lib.call: the executor puts them on a recording tape
+    itself."""
     __slots__ = ("cuda_event",)
 
     def __init__(self):
@@ -114,10 +137,12 @@ class ForkEvent:
         if rc != 0:
             raise AozoraError(f"az_event_record failed with code {rc}")
 
-    def wait_on(self, stream):
+    def wait(self, stream):
         rc = lib()._fn["az_stream_wait_event"](stream.cuda_stream, self.cuda_event)
         if rc != 0:
             raise AozoraError(f"az_stream_wait_event failed with code {rc}")
+
+    wait_on = wait
 
     def destroy(self):
         if self.cuda_event:

@@ -1,16 +1,16 @@
-"""Native launch tape (include/aozora_hip.h az_tape_*): the recorded launch sequence of a resolution bucket -- C-ABI calls,
-event records, stream waits -- compiled into a C-side tape and re-issued by az_tape_play without the interpreter; the host
-logic the executor marked as live (data-parallel region waits, scheduling hints, the end-of-backward join) stays Python and runs
-at the tape's BREAK operations.  SURVEY.md 8b names this seam `az_unet_step`; the reference issues the same sequence from
-Python / autograd every step (train.py:2743-2767)."""
+"""Native launch tape (include/aozora_hip.h az_tape_*).  The recorded launch sequence of a resolution bucket is a list of typed
+operations (_lib.Call / Record / Wait / Live): C-ABI calls by entry-point name, event records, stream waits, and the host logic the
+executor marked as live (data-parallel region waits, scheduling hints, the end-of-backward join).  fuse_records rewrites it,
+NativeTape compiles it into a C-side tape that az_tape_play re-issues without the interpreter -- the live operations stay Python
+and run at the tape's BREAK operations -- and replay issues it from Python.  All three branch on the kind of an operation and on
+nothing else.  SURVEY.md 8b names this seam `az_unet_step`; the reference issues the same sequence from Python / autograd every
+step (train.py:2743-2767)."""
 from __future__ import annotations
 
 import ctypes
 import struct
 
-import torch
-
-from ._lib import lib, AozoraError, ForkEvent
+from ._lib import lib, AozoraError, ForkEvent, Call, Record, Wait, Live
 
 OP_CALL, OP_EVENT_RECORD, OP_STREAM_WAIT, OP_BREAK = 0, 1, 2, 3
 
@@ -50,67 +50,55 @@ def fuse_records(recorded, only_stream=None):
     A second record on S with nothing queued on S since the first marks the same point: it is dropped and the waits on its event
     are re-pointed to the first event.  Anything else that touches S in between (another call, a wait, host logic) keeps the record.
     only_stream: fuse records on that stream only.  -> (new sequence, number of records fused)."""
-    L = lib()
-    by_fn = {id(fn): name for name, fn in L._fn.items()}
-    stream_arg = {name: [i for i, (_, an) in enumerate(args) if an == "stream"] for name, (_, args) in L.protos.items()}
-    set_ev = L._fn["az_set_launch_stop_event"]
-    out, fused = [], 0          # out: [entry, event handle or None]
+    stream_arg = {name: [i for i, (_, an) in enumerate(args) if an == "stream"] for name, (_, args) in lib().protos.items()}
+    out, fused = [], 0          # out: [operation, event handle or None]
     last = {}                   # stream handle -> index in out of the latest kernel-launching call on it, while nothing else touched the stream
     last_rec = {}               # stream handle -> the ForkEvent recorded on it last, while nothing else touched the stream since
     alias = {}                  # id(ForkEvent) -> the earlier ForkEvent that marks the same point of its stream (its record is dropped)
-    for fn, args in recorded:
-        name = by_fn.get(id(fn))
-        owner = getattr(fn, "__self__", None)
-        fname = getattr(fn, "__name__", "")
-        if name is not None:
-            idx = stream_arg.get(name) or []
-            out.append([(fn, args), None])
-            if not idx or len(L.protos[name][1]) != len(args):
+    for op in recorded:
+        if isinstance(op, Call):
+            idx = stream_arg.get(op.name)
+            out.append([op, None])
+            if not idx:
                 last.clear(); last_rec.clear()      # option changes, context calls ...: do not reason across them
             else:
-                st = _word("void*", args[idx[0]])
+                st = _word("void*", op.args[idx[0]])
                 last_rec.pop(st, None)
-                if name not in _KERNEL_ENTRIES:
+                if op.name not in _KERNEL_ENTRIES:
                     last.pop(st, None)
                 else:
                     last[st] = len(out) - 1
-            continue
-        if isinstance(owner, ForkEvent) and fname == "record":
-            st = args[0].cuda_stream
-            if only_stream is None or st == only_stream:
+        elif isinstance(op, Record):
+            ev, st = op.event, op.stream.cuda_stream
+            fork = isinstance(ev, ForkEvent)        # torch events are never fused
+            if fork and (only_stream is None or st == only_stream):
                 if st in last_rec:           # nothing was queued on the stream since the previous record: the same point of the stream
-                    alias[id(owner)] = last_rec[st]
+                    alias[id(ev)] = last_rec[st]
                     fused += 1
                     continue
                 k = last.pop(st, None)
                 if k is not None and out[k][1] is None:
-                    out[k][1] = owner.cuda_event
-                    last_rec[st] = owner
+                    out[k][1] = ev.cuda_event
+                    last_rec[st] = ev
                     fused += 1
                     continue
-            last.pop(st, None)
-            last_rec[st] = owner
-            out.append([(fn, args), None])
-            continue
-        if isinstance(owner, ForkEvent) and fname == "wait_on":
-            if id(owner) in alias:
-                fn = alias[id(owner)].wait_on
-            out.append([(fn, args), None])
-            last.pop(args[0].cuda_stream, None); last_rec.pop(args[0].cuda_stream, None)
-            continue
-        out.append([(fn, args), None])
-        if isinstance(owner, torch.cuda.Stream) and fname == "wait_event":
-            last.pop(owner.cuda_stream, None); last_rec.pop(owner.cuda_stream, None)
-        elif isinstance(owner, torch.cuda.Event) and fname == "record":
-            last.pop(args[0].cuda_stream, None); last_rec.pop(args[0].cuda_stream, None)
+            last.pop(st, None); last_rec.pop(st, None)
+            if fork:
+                last_rec[st] = ev
+            out.append([op, None])
+        elif isinstance(op, Wait):
+            st = op.stream.cuda_stream
+            out.append([Wait(op.stream, alias.get(id(op.event), op.event)), None])
+            last.pop(st, None); last_rec.pop(st, None)
         else:
+            out.append([op, None])
             last.clear(); last_rec.clear()   # host logic: anything may happen inside
     flat = []
-    for entry, ev in out:
+    for op, ev in out:
         if ev is None:
-            flat.append(entry)
+            flat.append(op)
         else:
-            flat += [(set_ev, (ctypes.c_void_p(ev),)), entry, (set_ev, (None,))]
+            flat += [Call("az_set_launch_stop_event", (ctypes.c_void_p(ev),)), op, Call("az_set_launch_stop_event", (None,))]
     return flat, fused
 
 
@@ -120,6 +108,30 @@ def disarm_stop_event():
     lib()._fn["az_set_launch_stop_event"](None)
 
 
+def issue(op):
+    """Issue one operation from Python."""
+    if isinstance(op, Call):
+        rc = lib()._fn[op.name](*op.args)
+        if rc:
+            raise AozoraError(f"{op.name} failed with code {rc} while re-issuing the launch tape")
+    elif isinstance(op, Record):
+        op.event.record(op.stream)
+    elif isinstance(op, Wait):
+        op.event.wait(op.stream)
+    else:
+        op.fn(*op.args)
+
+
+def replay(recorded):
+    """Re-issue a recorded sequence from Python (ExecPolicy.native_tape off)."""
+    try:
+        for op in recorded:
+            issue(op)
+    except BaseException:
+        disarm_stop_event()        # a failing operation between `set` and `clear` must not leave the event armed
+        raise
+
+
 class NativeTape:
     def __init__(self, recorded):
         L = lib()
@@ -127,8 +139,7 @@ class NativeTape:
         self.handle = ctypes.c_void_p()
         if L._fn["az_tape_create"](ctypes.byref(self.handle)):      # not through L.call: nothing here may land on a recording tape
             raise AozoraError("az_tape_create failed")
-        by_fn = {id(fn): name for name, fn in L._fn.items()}
-        self.callbacks = {}            # op index of a BREAK -> (callable, args)
+        self.callbacks = {}            # op index of a BREAK -> the operation to issue from Python there
         self.n = 0
         self.n_calls = 0
         add = L._fn["az_tape_add"]
@@ -140,27 +151,18 @@ class NativeTape:
                 raise AozoraError(f"az_tape_add failed with code {rc}")
             self.n += 1
 
-        for fn, args in recorded:
-            name = by_fn.get(id(fn))
-            if name is not None:
-                fid = L._fn["az_tape_fn_id"](name.encode())
-                protos = L.protos[name][1]
-                if fid >= 0 and len(protos) == len(args):
-                    push(OP_CALL, fid, [_word(t, a) for (t, _), a in zip(protos, args)])
-                    self.n_calls += 1
-                    continue
-            owner = getattr(fn, "__self__", None)
-            if isinstance(owner, (torch.cuda.Event, ForkEvent)) and getattr(fn, "__name__", "") == "record":
-                push(OP_EVENT_RECORD, 0, [owner.cuda_event, args[0].cuda_stream])
-                continue
-            if isinstance(owner, torch.cuda.Stream) and getattr(fn, "__name__", "") == "wait_event":
-                push(OP_STREAM_WAIT, 0, [owner.cuda_stream, args[0].cuda_event])
-                continue
-            if isinstance(owner, ForkEvent) and getattr(fn, "__name__", "") == "wait_on":
-                push(OP_STREAM_WAIT, 0, [args[0].cuda_stream, owner.cuda_event])
-                continue
-            self.callbacks[self.n] = (fn, args)       # host logic: runs in the caller at a BREAK
-            push(OP_BREAK, 0, [])
+        for op in recorded:
+            fid = L._fn["az_tape_fn_id"](op.name.encode()) if isinstance(op, Call) else -1
+            if fid >= 0:
+                push(OP_CALL, fid, [_word(t, a) for (t, _), a in zip(L.protos[op.name][1], op.args)])
+                self.n_calls += 1
+            elif isinstance(op, Record):
+                push(OP_EVENT_RECORD, 0, [op.event.cuda_event, op.stream.cuda_stream])
+            elif isinstance(op, Wait):
+                push(OP_STREAM_WAIT, 0, [op.stream.cuda_stream, op.event.cuda_event])
+            else:       # host logic, or an entry point outside the generated dispatch table: issued by the caller at a BREAK
+                self.callbacks[self.n] = op
+                push(OP_BREAK, 0, [])
         self._play = L._fn["az_tape_play"]
 
     def play(self):
@@ -180,11 +182,9 @@ class NativeTape:
                 raise AozoraError(f"native launch tape: operation {idx.value} failed with code {rc.value}")
             if nxt <= i:
                 raise AozoraError("native launch tape made no progress")
-            cb = self.callbacks.get(nxt - 1)
-            if cb is not None:
-                fn, args = cb
-                if fn(*args):
-                    raise AozoraError(f"{getattr(fn, '__name__', fn)} failed while re-issuing the launch tape")
+            op = self.callbacks.get(nxt - 1)
+            if op is not None:
+                issue(op)
             i = nxt
 
     def __del__(self):

@@ -25,7 +25,7 @@ import os
 import torch
 
 from . import ops
-from ._lib import lib, AozoraError, ForkEvent
+from ._lib import lib, AozoraError, ForkEvent, Record, Wait, Live
 from .unet_spec import UNetConfig, SDXL_BASE, param_table, up_resnet_channels
 
 @dataclass
@@ -392,9 +392,6 @@ class AozoraUNet:
         have landed.  Nothing may read them before wait_region_params(k)."""
         self._region_events[k] = ev
 
-    def set_tail_params_event(self, ev):
-        self.set_region_params_event(2, ev)
-
     def wait_region_params(self, k):
         ev = self._region_events.pop(k, None)
         if ev is not None:
@@ -405,15 +402,10 @@ class AozoraUNet:
             self._refresh_jobs(lo, hi)
             pend.discard(k)
 
-    def _wait_region1(self):
-        self.wait_region_params(1)
-
-    def _wait_region2(self):
-        self.wait_region_params(2)
-
-    def _run_region_hook1(self):
+    def _region_hook(self, k):
+        """Every gradient of region k has been issued.  Reads the hook at play time: TrainStep swaps it between replays."""
         if self._after_tail_hook is not None:
-            self._after_tail_hook(1)
+            self._after_tail_hook(k)
 
     # ---- host launch tape support: stream / event operations of the launch sequence go through these two so that a
     # recording (lib().recorder) captures them next to the ABI launches
@@ -421,30 +413,24 @@ class AozoraUNet:
         ev.record(stream)
         rec = lib().recorder
         if rec is not None:
-            rec.append((ev.record, (stream,)))
+            rec.append(Record(ev, stream))
 
     def _st_wait(self, stream, ev):
-        if isinstance(ev, ForkEvent):
-            ev.wait_on(stream)
-            rec = lib().recorder
-            if rec is not None:
-                rec.append((ev.wait_on, (stream,)))
-            return
-        stream.wait_event(ev)
+        ev.wait(stream)
         rec = lib().recorder
         if rec is not None:
-            rec.append((stream.wait_event, (ev,)))
+            rec.append(Wait(stream, ev))
 
-    def _live(self, fn):
-        """Run fn now with recording suspended and put fn itself on the tape (state-dependent host logic)."""
+    def _live(self, fn, *args):
+        """Run fn(*args) now with recording suspended and put the call itself on the tape (state-dependent host logic)."""
         L = lib()
         rec, L.recorder = L.recorder, None
         try:
-            fn()
+            fn(*args)
         finally:
             L.recorder = rec
         if rec is not None:
-            rec.append((fn, ()))
+            rec.append(Live(fn, args))
 
     def _end_join(self):
         """End of a backward.  Default: the data chain waits for the parameter-gradient stream(s).  With
@@ -469,15 +455,6 @@ class AozoraUNet:
 
     def has_deferred(self):
         return bool(self._deferred)
-
-    def _set_forward_exclusive(self):
-        # forward: the data chain has the CUs (and their LDS) to itself (kept so even with deferred weight-gradient work
-        # around: measured 0.851 vs 0.835 it/s)
-        lib().call("az_gemm_set_exclusive", 1)
-
-    def _run_after_tail(self):
-        if self._after_tail_hook is not None:
-            self._after_tail_hook(2)
 
     def wait_tail_params(self):
         """Wait for every in-flight parameter all-gather (name kept from the two-region form)."""
@@ -688,41 +665,46 @@ class AozoraUNet:
             self._ln_tables[key] = tab
         self._side_defer(lambda: ops.ln_param_finish_multi(tab[0], tab[1], tab[2]))
 
+    @staticmethod
+    def _linear_wgrad(dy, x, dW, bias_grad):
+        """dW += dY^T . X of a linear layer; the bias gradient (column sums of dY) rides on the same pass over dY."""
+        ops.gemm(dy, x, dW, trans_a=True, trans_b=False, accumulate=True, split_k=0, bias_grad=bias_grad)
+
+    def _queue_wgrads(self, jobs, grouped, tag=()):
+        """Queue parked linear weight gradients (dY, X, dW, bias gradient) on the parameter-gradient branch: as ONE grouped launch
+        whose job table is built once per operand set (`tag` keeps the keys of different callers apart), or one product each."""
+        if not grouped:
+            for job in jobs:
+                self._side_defer(lambda job=job: self._linear_wgrad(*job))
+            return
+        key = tag + tuple((dy.data_ptr(), xt.data_ptr(), GW.data_ptr(), bg.data_ptr() if bg is not None else 0) for dy, xt, GW, bg in jobs)
+        tab = self._tn_tables.get(key)
+        if tab is None:
+            tab = self._tn_tables[key] = ops.tn_group_table(jobs, self.device)
+        self._side_defer(lambda: ops.gemm_tn_grouped(*tab))
+
     def _finish_tn_jobs(self):
         """Queue the parked linear weight gradients on the parameter-gradient branch: as ONE grouped launch (every product over its
         whole k-range on 128x128 tiles -- no fp32 slabs, no reduce launches, the tiles of all products fill the chip together) when
         they add up to a chip-filling grid, else one split-K product each as before.  dY / X stay valid until the step ends: the
         activation pool never re-uses a buffer inside a step and a buffer that is some layer's dY is never written again (_gbuf)."""
         jobs, self._tn_jobs = self._tn_jobs, []
-        if not jobs:
-            return
-        tiles = sum(((dy.shape[1] + 127) // 128) * ((xt.shape[1] + 127) // 128) for dy, xt, _, _ in jobs)
-        if tiles < self.policy.tn_group:
-            for dy, xt, GW, bg in jobs:
-                self._side_defer(lambda dy=dy, xt=xt, GW=GW, bg=bg: ops.gemm(dy, xt, GW, trans_a=True, trans_b=False, accumulate=True, split_k=0, bias_grad=bg))
-            return
-        key = tuple((dy.data_ptr(), xt.data_ptr(), GW.data_ptr(), bg.data_ptr() if bg is not None else 0) for dy, xt, GW, bg in jobs)
-        tab = self._tn_tables.get(key)
-        if tab is None:
-            tab = ops.tn_group_table(jobs, self.device)
-            self._tn_tables[key] = tab
-        self._side_defer(lambda: ops.gemm_tn_grouped(*tab))
+        if jobs:
+            tiles = sum(((dy.shape[1] + 127) // 128) * ((xt.shape[1] + 127) // 128) for dy, xt, _, _ in jobs)
+            self._queue_wgrads(jobs, tiles >= self.policy.tn_group)
 
     def _finish_xkv_jobs(self):
         """The parked K / V projection weight gradients of a parameter region as ONE grouped launch on the branch (policy.xkv_group)."""
         jobs, self._xkv_jobs = self._xkv_jobs, []
-        if not jobs:
-            return
-        if len(jobs) == 1:
-            dy, xt, GW, bg = jobs[0]
-            self._side_defer(lambda: ops.gemm(dy, xt, GW, trans_a=True, trans_b=False, accumulate=True, split_k=0, bias_grad=bg))
-            return
-        key = ("xkv",) + tuple((dy.data_ptr(), xt.data_ptr(), GW.data_ptr(), bg.data_ptr() if bg is not None else 0) for dy, xt, GW, bg in jobs)
-        tab = self._tn_tables.get(key)
-        if tab is None:
-            tab = ops.tn_group_table(jobs, self.device)
-            self._tn_tables[key] = tab
-        self._side_defer(lambda: ops.gemm_tn_grouped(*tab))
+        if jobs:
+            self._queue_wgrads(jobs, len(jobs) > 1, ("xkv",))
+
+    def _region_end(self):
+        """A parameter region's backward is through: everything parked for the parameter-gradient branch goes out."""
+        self._finish_ln_jobs()
+        self._finish_tn_jobs()
+        self._finish_xkv_jobs()
+        self._flush_side()
 
     def _block_end(self):
         """Tape entry placed at the START of a block's forward (so it runs AFTER the block's backward): the block's parked
@@ -801,20 +783,20 @@ class AozoraUNet:
             else:
                 self._wait_ready(y)
             b_train = bname is not None and self._trainable(bname)
+            job = (dy, x.t, GW, self._gw[bname] if b_train else None)
 
             def wgrad():        # parameter gradients run as a free-running branch beside the data-gradient chain
-                if w_train:     # the bias gradient (column sums of dY) rides on the same pass over dY
-                    ops.gemm(dy, x.t, GW, trans_a=True, trans_b=False, accumulate=True, split_k=0,
-                             bias_grad=self._gw[bname] if b_train else None)
+                if w_train:
+                    self._linear_wgrad(*job)
                 elif b_train:
                     self._bias_grad(dy, bname, N)
             if w_train and pre is not None and w_override is not None and rows <= 512 and self.policy.xkv_group and self.concurrent_wgrad and not on_side:
                 # a hoisted context projection (K | V of a cross-attention): parked until the region's backward is through
-                self._xkv_jobs.append((dy, x.t, GW, self._gw[bname] if b_train else None))
+                self._xkv_jobs.append(job)
             elif w_train and self.policy.tn_group > 0 and 256 <= rows <= 8192 and not on_side:
                 # parked until the parked products add up to a chip-filling grid (attn2.to_out + attn2.to_q; attn1.to_out + to_q|k|v;
                 # the feed-forward ones are that large on their own), then ONE grouped launch, every product over its whole k-range
-                self._tn_jobs.append((dy, x.t, GW, self._gw[bname] if b_train else None))
+                self._tn_jobs.append(job)
                 if sum(((j[0].shape[1] + 127) // 128) * ((j[1].shape[1] + 127) // 128) for j in self._tn_jobs) >= self.policy.tn_group:
                     self._finish_tn_jobs()
             elif w_train or b_train:
@@ -835,6 +817,12 @@ class AozoraUNet:
                 self._give_grad(residual, dy)
         self._tape.append(bwd)
         return y
+
+    @staticmethod
+    def _as3(t: torch.Tensor, B, HW):
+        """[B*HW][C] row view (any row stride) -> (B,HW,C) view."""
+        ld = t.stride(0)
+        return t.as_strided((B, HW, t.shape[1]), (HW * ld, ld, 1))
 
     @staticmethod
     def _as4(t: torch.Tensor, B, H, W_):
@@ -917,7 +905,7 @@ class AozoraUNet:
         y = self._new(B * H * W_, C)
         stats = self._pool.get((B * G * 2,), F32)
         gam, bet = self._w[prefix + ".weight"], self._w[prefix + ".bias"]
-        x3 = x.t.as_strided((B, H * W_, C), (H * W_ * x.t.stride(0), x.t.stride(0), 1))
+        x3 = self._as3(x.t, B, H * W_)
         ops.groupnorm_fwd(x3, gam, bet, y.t.view(B, H * W_, C), stats, G, eps, silu)
 
         def bwd():
@@ -925,13 +913,13 @@ class AozoraUNet:
             if dy is None:
                 return
             tg, tb = self._trainable(prefix + ".weight"), self._trainable(prefix + ".bias")
-            dy3 = dy.as_strided((B, H * W_, C), (H * W_ * dy.stride(0), dy.stride(0), 1))
+            dy3 = self._as3(dy, B, H * W_)
             dx3, add3 = None, None
             if x.need_grad:
                 dx, add = self._gbuf(x)
-                dx3 = dx.as_strided((B, H * W_, C), (H * W_ * dx.stride(0), dx.stride(0), 1))
+                dx3 = self._as3(dx, B, H * W_)
                 if add is not None:
-                    add3 = add.as_strided((B, H * W_, C), (H * W_ * add.stride(0), add.stride(0), 1))
+                    add3 = self._as3(add, B, H * W_)
             ops.groupnorm_bwd(x3, gam, bet, stats, dy3, dx3, self._gw[prefix + ".weight"] if tg else None,
                               self._gw[prefix + ".bias"] if tb else None, G, silu, dx_add=add3)
         self._tape.append(bwd)
@@ -1256,7 +1244,9 @@ class AozoraUNet:
         ch = cfg.block_out_channels
         nlev = len(ch)
         T = cfg.time_embed_dim
-        self._live(self._set_forward_exclusive)
+        # forward: the data chain has the CUs (and their LDS) to itself (kept so even with deferred weight-gradient work
+        # around: measured 0.851 vs 0.835 it/s)
+        self._live(lib().call, "az_gemm_set_exclusive", 1)
         # ---- embeddings (a7.1) ----
         tsin = self._new(B, ch[0], need_grad=False)
         ops.timestep_embed(t_f32, ch[0], tsin.t)
@@ -1310,7 +1300,7 @@ class AozoraUNet:
             pre = f"down_blocks.{i}"
             if i == nlev - 1:
                 self._tape_mark1 = len(self._tape)     # backward entries in [mark1, mark) belong to the last down block (region 1)
-                self._live(self._wait_region1)         # DP overlap: region 1's all-gather must have landed by now
+                self._live(self.wait_region_params, 1)  # DP overlap: region 1's all-gather must have landed by now
                 self._hoist_shared_input_linears(self._region_blocks(1), ctx_a, emb_s)
             rows = geom[0] * geom[1] * geom[2]
             for j in range(lpb):
@@ -1326,7 +1316,7 @@ class AozoraUNet:
                 skips.append(h)
         # ---- mid ----
         self._tape_mark = len(self._tape)       # backward entries >= mark belong to mid / up / head-out (the "tail" region)
-        self._live(self._wait_region2)          # DP overlap: the tail parameters' all-gather must have landed by now
+        self._live(self.wait_region_params, 2)  # DP overlap: the tail parameters' all-gather must have landed by now
         self._hoist_shared_input_linears(self._region_blocks(2), ctx_a, emb_s)
         h = self.resnet(h, geom, emb_s, "mid_block.resnets.0")
         h = self.transformer(h, geom, ctx_a, L, "mid_block.attentions.0", cfg.transformer_layers[-1])
@@ -1362,22 +1352,13 @@ class AozoraUNet:
         self._after_tail_hook = after_tail
         for idx in range(len(self._tape) - 1, -1, -1):
             if idx == mark - 1:
-                self._finish_ln_jobs()
-                self._finish_tn_jobs()
-                self._finish_xkv_jobs()
-                self._flush_side()
-                self._live(self._run_after_tail)   # every gradient of region 2 has been issued (main + side stream)
+                self._region_end()
+                self._live(self._region_hook, 2)   # every gradient of region 2 has been issued (main + side stream)
             if idx == mark1 - 1:
-                self._finish_ln_jobs()
-                self._finish_tn_jobs()
-                self._finish_xkv_jobs()
-                self._flush_side()
-                self._live(self._run_region_hook1) # ... and now those of region 1 (the last down block)
+                self._region_end()
+                self._live(self._region_hook, 1)   # ... and now those of region 1 (the last down block)
             self._tape[idx]()
-        self._finish_ln_jobs()
-        self._finish_tn_jobs()
-        self._finish_xkv_jobs()
-        self._flush_side()
+        self._region_end()
         self._tape = []
         if self.concurrent_wgrad and self._side_used:      # join the parameter-gradient branches (or let them run on)
             self._live(self._end_join)

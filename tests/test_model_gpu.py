@@ -669,7 +669,7 @@ def test_context_calls_never_land_on_a_recording_launch_tape(setup):
     recorder: a UNet that is created, stepped or garbage-collected while ANOTHER step records its tape must not leave an
     az_destroy (a double free on every replay) or an az_make_current on it."""
     import gc
-    from aozora_sdxl_training_amd._lib import lib
+    from aozora_sdxl_training_amd._lib import lib, Call
     from aozora_sdxl_training_amd.unet import AozoraUNet
     pc, oc, params, unet = setup
     L = lib()
@@ -680,8 +680,7 @@ def test_context_calls_never_land_on_a_recording_launch_tape(setup):
         tmp.begin_step(("probe",))
         del tmp
         gc.collect()
-        names = {id(fn): n for n, fn in L._fn.items()}
-        taped = [names.get(id(fn), "?") for fn, _ in L.recorder]
+        taped = [op.name for op in L.recorder if isinstance(op, Call)]
     finally:
         L.recorder = None
     assert not [n for n in taped if n in ("az_init", "az_make_current", "az_destroy")], taped
