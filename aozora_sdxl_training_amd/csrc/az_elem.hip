@@ -84,17 +84,20 @@ __global__ void add_rows_kernel(long rows, int Cc, const bf16_t* __restrict__ a,
   }
 }
 
-__global__ void upsample_fwd_kernel(int B, int H, int W, int Cc, const bf16_t* __restrict__ x, bf16_t* __restrict__ y) {
-  long n = (long)B * (2 * H) * (2 * W) * Cc;
+// nearest upsample to Ho x Wo with Ho in {2H - 1, 2H}, Wo in {2W - 1, 2W}: source index dst >> 1 (what F.interpolate(size=, mode="nearest")
+// computes for both targets), i.e. the nearest-2x image with its last row / column cropped
+__global__ void upsample_fwd_kernel(int B, int H, int W, int Ho, int Wo, int Cc, const bf16_t* __restrict__ x, bf16_t* __restrict__ y) {
+  long n = (long)B * Ho * Wo * Cc;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     int c = (int)(i % Cc); long p = i / Cc;
-    int ox = (int)(p % (2 * W)); p /= (2 * W);
-    int oy = (int)(p % (2 * H)); int b = (int)(p / (2 * H));
+    int ox = (int)(p % Wo); p /= Wo;
+    int oy = (int)(p % Ho); int b = (int)(p / Ho);
     const bf16_t* src = x + (((long)b * H + (oy >> 1)) * W + (ox >> 1)) * (Cc * 8L) + c * 8;
     *reinterpret_cast<uint4*>(y + i * 8) = *reinterpret_cast<const uint4*>(src);
   }
 }
-__global__ void upsample_bwd_kernel(int B, int H, int W, int Cc, const bf16_t* __restrict__ dy, bf16_t* __restrict__ dx) {
+// its adjoint: the 2x2 fold in which a source pixel on a cropped edge receives 2 or 1 contributions instead of 4 (dy-row major, fp32, one rounding)
+__global__ void upsample_bwd_kernel(int B, int H, int W, int Ho, int Wo, int Cc, const bf16_t* __restrict__ dy, bf16_t* __restrict__ dx) {
   long n = (long)B * H * W * Cc;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     int c = (int)(i % Cc); long p = i / Cc;
@@ -105,8 +108,9 @@ __global__ void upsample_bwd_kernel(int B, int H, int W, int Cc, const bf16_t* _
     for (int dyy = 0; dyy < 2; ++dyy)
 #pragma unroll
       for (int dxx = 0; dxx < 2; ++dxx) {
+        if (2 * y0 + dyy >= Ho || 2 * x0 + dxx >= Wo) continue;
         float f[8];
-        unpack8(*reinterpret_cast<const uint4*>(dy + (((long)b * 2 * H + 2 * y0 + dyy) * (2 * W) + 2 * x0 + dxx) * (Cc * 8L) + c * 8), f);
+        unpack8(*reinterpret_cast<const uint4*>(dy + (((long)b * Ho + 2 * y0 + dyy) * Wo + 2 * x0 + dxx) * (Cc * 8L) + c * 8), f);
 #pragma unroll
         for (int e = 0; e < 8; ++e) s[e] += f[e];
       }
@@ -477,17 +481,31 @@ int az_add_rows(long rows, int C, const void* a, long lda, const void* b, long l
   AZ_CHECK_LAUNCH();
   return AZ_OK;
 }
+int az_upsample_nearest_fwd(int batch, int H, int W, int Hout, int Wout, int C, const void* x, void* y, void* stream) {
+  if ((C & 7) || batch <= 0 || H <= 0 || W <= 0 || (Hout != 2 * H && Hout != 2 * H - 1) || (Wout != 2 * W && Wout != 2 * W - 1)) return AZ_ERR_ARG(43);
+  long n = (long)batch * Hout * Wout * (C / 8);
+  az_launch(upsample_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, batch, H, W, Hout, Wout, C / 8, (const bf16_t*)x, (bf16_t*)y);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+int az_upsample_nearest_bwd(int batch, int H, int W, int Hout, int Wout, int C, const void* dy, void* dx, void* stream) {
+  if ((C & 7) || batch <= 0 || H <= 0 || W <= 0 || (Hout != 2 * H && Hout != 2 * H - 1) || (Wout != 2 * W && Wout != 2 * W - 1)) return AZ_ERR_ARG(43);
+  long n = (long)batch * H * W * (C / 8);
+  az_launch(upsample_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, batch, H, W, Hout, Wout, C / 8, (const bf16_t*)dy, (bf16_t*)dx);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
 int az_upsample2x_fwd(int batch, int H, int W, int C, const void* x, void* y, void* stream) {
   if (C & 7) return AZ_ERR_ARG(43);
   long n = (long)batch * 4 * H * W * (C / 8);
-  az_launch(upsample_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, batch, H, W, C / 8, (const bf16_t*)x, (bf16_t*)y);
+  az_launch(upsample_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, batch, H, W, 2 * H, 2 * W, C / 8, (const bf16_t*)x, (bf16_t*)y);
   AZ_CHECK_LAUNCH();
   return AZ_OK;
 }
 int az_upsample2x_bwd(int batch, int H, int W, int C, const void* dy, void* dx, void* stream) {
   if (C & 7) return AZ_ERR_ARG(43);
   long n = (long)batch * H * W * (C / 8);
-  az_launch(upsample_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, batch, H, W, C / 8, (const bf16_t*)dy, (bf16_t*)dx);
+  az_launch(upsample_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, batch, H, W, 2 * H, 2 * W, C / 8, (const bf16_t*)dy, (bf16_t*)dx);
   AZ_CHECK_LAUNCH();
   return AZ_OK;
 }

@@ -47,8 +47,10 @@ struct Geom {          // convolution geometry (all modes that gather)
   int Hout, Wout, Cout;// conv output grid / channels (Y)
   int stride, pad, ks; // ks in {1,3}
   int cpad;            // channel count used to split k into (tap, c) for CONVT/CONVDG (>= real count)
-  int ups;             // 1: X is stored at HALF resolution (Hin/2 x Win/2) and read through a nearest-neighbour 2x gather
-                       //    (diffusers Upsample2D: F.interpolate(scale_factor=2, mode="nearest") -> conv)
+  int ups;             // 1: X is stored at HALF resolution (Hsrc x Wsrc) and read through a nearest-neighbour 2x gather
+                       //    (diffusers Upsample2D: F.interpolate(scale_factor=2 | size=, mode="nearest") -> conv)
+  int Hsrc, Wsrc;      // stored extents of X: Hin x Win, with ups ceil(Hin / 2) x ceil(Win / 2) -- an odd Hin / Win is the nearest-2x
+                       //    image with its last row / column cropped (F.interpolate(size=) to 2n - 1: source index is still dst >> 1)
 };
 
 struct Params {
@@ -320,8 +322,8 @@ struct ALoader {
         const int ky = (p.g.ks == 3) ? tap / 3 : 0, kx = (p.g.ks == 3) ? tap - 3 * ky : 0;
         const int iy = pix_y[j] * p.g.stride + ky - p.g.pad, ix = pix_x[j] * p.g.stride + kx - p.g.pad;
         const bool ok = k < p.K && iy >= 0 && iy < p.g.Hin && ix >= 0 && ix < p.g.Win;
-        const int u = p.g.ups;     // nearest-2x: source pixel (iy >> 1, ix >> 1) of the half-resolution tensor
-        off = ok ? (unsigned)((pix_b[j] * (p.g.Hin >> u) + (iy >> u)) * (p.g.Win >> u) + (ix >> u)) * (unsigned)p.lda2 + (unsigned)ci * 2u : OOB;
+        const int u = p.g.ups;     // nearest-2x: source pixel (iy >> 1, ix >> 1) of the half-resolution tensor; a tap beyond a cropped edge is padding (ok)
+        off = ok ? (unsigned)((pix_b[j] * p.g.Hsrc + (iy >> u)) * p.g.Wsrc + (ix >> u)) * (unsigned)p.lda2 + (unsigned)ci * 2u : OOB;
       } else {  // A_CONVT : rows = conv-input pixels, source = dY (Hout,Wout,cpad)
         const int k = k0 + kc[j] * 8;
         const int tap = p.tap_uniform ? k0 / p.g.cpad : k / p.g.cpad;
@@ -444,7 +446,7 @@ struct BLoader {
         const int iy = oy * p.g.stride + tap_ky[j] - p.g.pad, ix = ox * p.g.stride + tap_kx[j] - p.g.pad;
         ok = ok && iy >= 0 && iy < p.g.Hin && ix >= 0 && ix < p.g.Win;
         const int u = p.g.ups;
-        off = ok ? (unsigned)((b * (p.g.Hin >> u) + (iy >> u)) * (p.g.Win >> u) + (ix >> u)) * (unsigned)p.ldb2 + (unsigned)ci[j] * 2u : OOB;
+        off = ok ? (unsigned)((b * p.g.Hsrc + (iy >> u)) * p.g.Wsrc + (ix >> u)) * (unsigned)p.ldb2 + (unsigned)ci[j] * 2u : OOB;
       }
       dma16(rs, off, dst);
     }
@@ -1512,14 +1514,14 @@ static int conv_impl(int mode, int batch, int Hin, int Win, int Cin, int Hout, i
                    long ldo, const void* bias, const void* rowbias, long ld_rowbias, const void* residual, long ldr,
                    int accumulate, int split_k, void* workspace, long workspace_bytes, void* bias_grad, void* seg_grad,
                    void* stream) {
-  const int ups = (mode >> 4) & 1;       // mode | 16: X is the half-resolution input of a nearest-2x upsample (forward / weight gradient)
+  const int ups = (mode >> 4) & 1;       // mode | 16: X is the half-resolution input [ceil(Hin/2)][ceil(Win/2)] of a nearest upsample to Hin x Win (forward / weight gradient)
   mode &= 15;
-  if (ups && ((mode != 0 && mode != 2) || ksize != 3 || stride != 1 || (Hin & 1) || (Win & 1))) return AZ_ERR_ARG(23);
+  if (ups && ((mode != 0 && mode != 2) || ksize != 3 || stride != 1)) return AZ_ERR_ARG(23);
   if (ksize != 1 && ksize != 3) return AZ_ERR_ARG(10);
   if (stride != 1 && stride != 2) return AZ_ERR_ARG(11);
   if ((Cin & 7)) return AZ_ERR_ARG(12);
   Params p{};
-  p.g = Geom{Hin, Win, Cin, Hout, Wout, Cout, stride, pad, ksize, cpad > 0 ? cpad : Cout, ups};
+  p.g = Geom{Hin, Win, Cin, Hout, Wout, Cout, stride, pad, ksize, cpad > 0 ? cpad : Cout, ups, (Hin + ups) >> ups, (Win + ups) >> ups};
   const int taps = ksize * ksize;
   p.bias = (const bf16_t*)bias; p.accumulate = accumulate; p.ws = (float*)workspace;
   p.rowbias = (const bf16_t*)rowbias; p.ld_rb = ld_rowbias; p.R = (const bf16_t*)residual; p.ldr = ldr;

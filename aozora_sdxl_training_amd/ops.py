@@ -231,13 +231,21 @@ def _nhwc(t: torch.Tensor):
     return B, H, W, C, ld
 
 
+def _upsampled_extents(H, W, t):
+    """Target extents of a nearest upsample of an H x W grid, taken from the (B,Ho,Wo,C) tensor at that resolution."""
+    _req(t.dim() == 4 and t.shape[1] in (2 * H - 1, 2 * H) and t.shape[2] in (2 * W - 1, 2 * W),
+         f"upsample target {tuple(t.shape[1:3])} must be (2H or 2H-1, 2W or 2W-1) of the source {(H, W)}")
+    return t.shape[1], t.shape[2]
+
+
 def conv_fwd(x, w, out, *, stride=1, bias=None, rowbias=None, residual=None, upsample=False):
     """x (B,H,W,Cin) ; w [Cout][k][k][Cin] contiguous ; out (B,Ho,Wo,Cout).
-    upsample: x is the HALF-resolution input of a nearest-2x upsample (Upsample2D); the conv reads it through the gather."""
+    upsample: x is the HALF-resolution input of a nearest upsample (Upsample2D) to out's extents, each 2H or 2H - 1 / 2W or 2W - 1
+    (F.interpolate(scale_factor=2) / (size=): the 2x image with its last row / column cropped); the conv reads it through the gather."""
     B, H, W, Cin, ldx = _nhwc(x)
     if upsample:
         _req(stride == 1 and w.shape[1] == 3, "the upsample gather exists for 3x3 stride-1 convolutions")
-        H, W = 2 * H, 2 * W
+        H, W = _upsampled_extents(H, W, out)
     _req(w.dtype == BF16 and w.is_contiguous() and w.dim() == 4 and w.shape[3] == Cin and w.shape[1] == w.shape[2], "weight layout")
     Cout, ks = w.shape[0], w.shape[1]
     pad = 1 if ks == 3 else 0
@@ -293,17 +301,17 @@ def conv_dgrad_wt(dy, wt, dx, *, stride=1, accumulate=False, residual=None):
 def conv_wgrad(dy, x, dw, *, stride=1, cout_real=None, accumulate=True, split_k=0, bias_grad=None, seg_grad=None, upsample=False):
     """dw [Cout][k][k][Cin] (+)= dy^T . im2col(x).  bias_grad (bf16 [Cout], +=) and seg_grad (bf16 [B][Cout], overwritten:
     per-sample channel sums of dy) are produced in the same pass when given.  upsample: x is the half-resolution input of a
-    nearest-2x upsample in front of the conv."""
+    nearest upsample to dy's extents (see conv_fwd) in front of the conv."""
     B, Ho, Wo, Cdy, lddy = _nhwc(dy)
     Bx, H, W, Cin, ldx = _nhwc(x)
     if upsample:
         _req(stride == 1 and dw.shape[1] == 3, "the upsample gather exists for 3x3 stride-1 convolutions")
-        H, W = 2 * H, 2 * W
+        H, W = _upsampled_extents(H, W, dy)
     Cout = Cdy if cout_real is None else cout_real
     _req(dw.dtype == BF16 and dw.is_contiguous() and dw.dim() == 4 and dw.shape[0] == Cout and dw.shape[3] == Cin, "dw layout")
     ks = dw.shape[1]
     pad = 1 if ks == 3 else 0
-    _req(Bx == B and Ho == (H + 2 * pad - ks) // stride + 1, "geometry")
+    _req(Bx == B and Ho == (H + 2 * pad - ks) // stride + 1 and Wo == (W + 2 * pad - ks) // stride + 1, "geometry")
     _req(lddy >= ((Cout + 7) // 8) * 8, "dy rows must be readable in 8-element chunks")
     ws = workspace(dw.device)
     if bias_grad is not None or seg_grad is not None:
@@ -521,6 +529,28 @@ def upsample2x_bwd(dy, dx):
     _req(dx.is_contiguous() and dy.is_contiguous() and tuple(dy.shape) == (B, 2 * H, 2 * W, C), "upsample bwd")
     with _prof('upsample', 0.0, 10.0 * B * H * W * C):
         lib().call("az_upsample2x_bwd", B, H, W, C, _ptr(dy), _ptr(dx), _stream())
+    return dx
+
+
+def upsample_nearest_fwd(x, y):
+    """x (B,H,W,C) -> y (B,Ho,Wo,C) with Ho in {2H-1, 2H}, Wo in {2W-1, 2W}: F.interpolate(size=(Ho, Wo), mode="nearest")."""
+    B, H, W, C = x.shape
+    _req(x.is_contiguous() and y.is_contiguous() and y.dim() == 4 and (y.shape[0], y.shape[3]) == (B, C) and x.dtype == BF16 and y.dtype == BF16,
+         "sized upsample")
+    Ho, Wo = _upsampled_extents(H, W, y)
+    with _prof('upsample', 0.0, 2.5 * B * Ho * Wo * C):
+        lib().call("az_upsample_nearest_fwd", B, H, W, Ho, Wo, C, _ptr(x), _ptr(y), _stream())
+    return y
+
+
+def upsample_nearest_bwd(dy, dx):
+    """The adjoint of upsample_nearest_fwd: dx (B,H,W,C) = the 2x2 fold of dy (B,Ho,Wo,C), cropped edges receiving fewer terms."""
+    B, H, W, C = dx.shape
+    _req(dx.is_contiguous() and dy.is_contiguous() and dy.dim() == 4 and (dy.shape[0], dy.shape[3]) == (B, C) and dx.dtype == BF16 and dy.dtype == BF16,
+         "sized upsample bwd")
+    Ho, Wo = _upsampled_extents(H, W, dy)
+    with _prof('upsample', 0.0, 2.5 * B * Ho * Wo * C):
+        lib().call("az_upsample_nearest_bwd", B, H, W, Ho, Wo, C, _ptr(dy), _ptr(dx), _stream())
     return dx
 
 

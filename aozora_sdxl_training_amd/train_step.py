@@ -239,6 +239,7 @@ class TrainStep:
         u = self.unet
         B, C, H, W = latents.shape
         L = embeds.shape[1]
+        u.check_latent_shape(H, W)
         if defer_join and not self.double_buffer:
             raise AozoraError("defer_join needs TrainStep(double_buffer=True) and the eager executor")
         parity = self._parity if self.double_buffer else 0

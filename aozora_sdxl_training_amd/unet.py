@@ -183,6 +183,7 @@ class _UNetCall(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, unet, sample, t_f32, ehs, pooled, tids_f32):
         B, C, H, W = sample.shape
+        unet.check_latent_shape(H, W)
         unet.begin_step((B, H, W, ehs.shape[1], "call"))
         x8 = unet._pool.get((B, H, W, 8), BF16)
         ops.nchw_to_nhwc_pad(sample.contiguous(), x8, C)
@@ -906,14 +907,23 @@ class AozoraUNet:
         return t.as_strided((B, H, W_, t.shape[1]), (H * W_ * ld, W_ * ld, ld, 1))
 
     def conv(self, x: Act, geom, wname, bname, stride=1, rowbias: Optional[Act] = None, residual: Optional[Act] = None,
-             upsample=False, out: Optional[Act] = None) -> Tuple[Act, tuple]:
+             upsample=False, out: Optional[Act] = None, up_to: Optional[Tuple[int, int]] = None) -> Tuple[Act, tuple]:
         """3x3 conv (pad 1). The gradient handed to this op may carry more (zero) channels than Cout
         (conv_out: dpred is padded 4 -> 8 so that rows stay 16-byte chunks).
         upsample (Upsample2D): `geom` is x's own (half) resolution; forward and weight gradient read x through a
         nearest-2x gather inside the operand fetch, so the upsampled activation never exists; the data gradient comes out at
-        the upsampled resolution into a scratch gradient and is folded 2x2 -> 1 by az_upsample2x_bwd."""
+        the upsampled resolution into a scratch gradient and is folded 2x2 -> 1 by az_upsample2x_bwd.
+        up_to: the upsample's target (H, W), each side 2n or 2n - 1 of x's (the skip tensor's geometry the result is concatenated
+        with: F.interpolate(size=), the 2x image with its last row / column cropped); None: 2x.  The scratch gradient then has the
+        cropped resolution and az_upsample_nearest_bwd folds it."""
         B, Hs, Ws = geom
-        H, W_ = (2 * Hs, 2 * Ws) if upsample else (Hs, Ws)
+        if upsample:
+            H, W_ = up_to if up_to is not None else (2 * Hs, 2 * Ws)
+            if H not in (2 * Hs - 1, 2 * Hs) or W_ not in (2 * Ws - 1, 2 * Ws):
+                raise AozoraError(f"upsample target {(H, W_)} is not (2n or 2n-1) of {(Hs, Ws)}")
+        else:
+            H, W_ = Hs, Ws
+        cropped = upsample and (H, W_) != (2 * Hs, 2 * Ws)
         Wt = self._w[wname]
         Cout, ks, _, Cin = Wt.shape
         Ho = (H + 2 - 3) // stride + 1
@@ -966,7 +976,9 @@ class AozoraUNet:
                     ops.conv_dgrad_wt(dy4, wt, self._as4(dx, B, H, W_), stride=stride, accumulate=add is dx, residual=res4)
                 else:
                     ops.conv_dgrad(dy4, Wt, self._as4(dx, B, H, W_), stride=stride, cout_real=Cout, accumulate=add is dx, residual=res4)
-                if upsample:
+                if cropped:
+                    ops.upsample_nearest_bwd(dx.view(B, H, W_, Cin), dxs.view(B, Hs, Ws, Cin))
+                elif upsample:
                     ops.upsample2x_bwd(dx.view(B, H, W_, Cin), dxs.view(B, Hs, Ws, Cin))
             if residual is not None:
                 self._give_grad(residual, dy)
@@ -1264,11 +1276,13 @@ class AozoraUNet:
         self._tape.append(bwd)
         return y
 
-    def upsample(self, x: Act, geom) -> Tuple[Act, tuple]:
+    def upsample(self, x: Act, geom, up_to: Optional[Tuple[int, int]] = None) -> Tuple[Act, tuple]:
+        """Stand-alone nearest upsample to `up_to` (H, W) (each side 2n or 2n - 1; None: 2x) and its adjoint."""
         B, H, W_ = geom
         C = x.t.shape[1]
-        y = self._new(B * 4 * H * W_, C)
-        ops.upsample2x_fwd(x.t.view(B, H, W_, C), y.t.view(B, 2 * H, 2 * W_, C))
+        Ho, Wo = up_to if up_to is not None else (2 * H, 2 * W_)
+        y = self._new(B * Ho * Wo, C)
+        ops.upsample_nearest_fwd(x.t.view(B, H, W_, C), y.t.view(B, Ho, Wo, C))
 
         def bwd():
             if y.g is None:
@@ -1276,9 +1290,9 @@ class AozoraUNet:
             dx = self._gbuf_single(x, "upsample input")
             if not y.g.is_contiguous():
                 raise AozoraError("upsample gradient must be contiguous")
-            ops.upsample2x_bwd(y.g.view(B, 2 * H, 2 * W_, C), dx.view(B, H, W_, C))
+            ops.upsample_nearest_bwd(y.g.view(B, Ho, Wo, C), dx.view(B, H, W_, C))
         self._tape.append(bwd)
-        return y, (B, 2 * H, 2 * W_)
+        return y, (B, Ho, Wo)
 
     # ------------------------------------------------------------------ whole model ---------------
     def __del__(self):
@@ -1342,6 +1356,14 @@ class AozoraUNet:
                 "need": {k: p.nbytes() for k, p in self._pools.items()},
                 "generation": self.generation}
 
+    def check_latent_shape(self, H: int, W: int):
+        """Every latent size whose sides hold one pixel per level of the coarsest grid runs (SDXL: H, W >= 4); a side that is no
+        multiple of 2**(levels - 1) comes back up through size-targeted upsamples (forward_nhwc).  Smaller ones are refused here,
+        before anything is launched."""
+        lo = 2 ** (len(self.cfg.block_out_channels) - 1)
+        if H < lo or W < lo:
+            raise AozoraError(f"latent shape {H}x{W} cannot run: each side must be at least {lo}")
+
     def begin_step(self, key):
         lib()._fn["az_make_current"](self._ctx)      # this thread's launches read THIS UNet's option table from here on
         arena = self._arena_of(key[-1])
@@ -1369,6 +1391,7 @@ class AozoraUNet:
         time_ids_f32 (B,6) fp32 (values already rounded through bf16, train.py:2731). -> pred Act [B*H*W][4]"""
         cfg = self.cfg
         B, H, W_, _ = x8.shape
+        self.check_latent_shape(H, W_)
         L = ctx.shape[1]
         ch = cfg.block_out_channels
         nlev = len(ch)
@@ -1422,6 +1445,7 @@ class AozoraUNet:
             return Act(cat.t[:, :c1_of(u)]) if cat is not None else None
 
         skips: List[Act] = []
+        level_geom = [geom]      # geometry of every level on the way down: the up path's upsamplers return to exactly these
         h, _ = self.conv(xin, geom, "conv_in.weight", "conv_in.bias", out=skip_dest(B * H * W_, ch[0]))
         self._hoist_shared_input_linears(self._region_blocks(0), ctx_a, emb_s)
         skips.append(h)
@@ -1440,8 +1464,10 @@ class AozoraUNet:
                     h = self.resnet(h, geom, emb_s, f"{pre}.resnets.{j}", out=skip_dest(rows, ch[i]))
                 skips.append(h)
             if i < nlev - 1:
+                Hd, Wd = (geom[1] - 1) // 2 + 1, (geom[2] - 1) // 2 + 1      # 3x3, stride 2, pad 1: ceil(side / 2)
                 h, geom = self.conv(h, geom, f"{pre}.downsamplers.0.conv.weight", f"{pre}.downsamplers.0.conv.bias", stride=2,
-                                    out=skip_dest(rows // 4, ch[i]))
+                                    out=skip_dest(geom[0] * Hd * Wd, ch[i]))
+                level_geom.append(geom)
                 skips.append(h)
         # ---- mid ----
         self._tape_mark = len(self._tape)       # backward entries >= mark belong to mid / up / head-out (the "tail" region)
@@ -1464,8 +1490,9 @@ class AozoraUNet:
                     h = self.transformer(h, geom, ctx_a, L, f"{pre}.attentions.{j}", cfg.transformer_layers[lev], out=nxt)
                 else:
                     h = self.resnet(h, geom, emb_s, f"{pre}.resnets.{j}", out=nxt)
-            if i < nlev - 1:       # Upsample2D: nearest-2x folded into the conv's operand gather
-                h, geom = self.conv(h, geom, f"{pre}.upsamplers.0.conv.weight", f"{pre}.upsamplers.0.conv.bias", upsample=True, out=up_dest(u))
+            if i < nlev - 1:       # Upsample2D: nearest upsample to the geometry of the skip tensor it meets next, folded into the conv's operand gather
+                h, geom = self.conv(h, geom, f"{pre}.upsamplers.0.conv.weight", f"{pre}.upsamplers.0.conv.bias", upsample=True, out=up_dest(u),
+                                    up_to=level_geom[lev - 1][1:])
         n = self.groupnorm(h, geom, "conv_norm_out", 1e-5, True)
         pred, _ = self.conv(n, geom, "conv_out.weight", "conv_out.bias")
         return pred

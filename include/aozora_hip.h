@@ -151,10 +151,12 @@ int az_gemm_wgrad_bias_bf16(int M, int N, int K, const void* dY, long lddy, cons
  *   mode 2 wgrad   : out = dW[Cout][k][k][Cin] from dY, X   (accumulate / split_k as az_gemm_bf16)
  *   mode 3 dgrad   : as mode 1 but W is the pre-transposed copy W'[Cin][ky][kx][Cout] (Cout % 8 == 0): NT-form product
  * `cpad` (mode 1): channel count dY rows are padded to (>= Cout, multiple of 8; 0 => Cout).
- * mode | 16 (with mode 0 or 2, 3x3, stride 1): X is stored at HALF resolution [B][Hin/2][Win/2][Cin] and is read through a
- *   nearest-neighbour 2x gather -- diffusers Upsample2D (F.interpolate(scale_factor=2, mode="nearest") followed by the conv)
- *   without materialising the upsampled tensor; Hin / Win stay the UPSAMPLED extents.  az_conv2d_wgrad_bias_bf16 takes the same
- *   flag as ksize | 16.
+ * mode | 16 (with mode 0 or 2, 3x3, stride 1): X is stored at HALF resolution [B][ceil(Hin/2)][ceil(Win/2)][Cin] and is read
+ *   through a nearest-neighbour gather (source pixel (y >> 1, x >> 1)) -- diffusers Upsample2D (F.interpolate(mode="nearest")
+ *   followed by the conv) without materialising the upsampled tensor; Hin / Win stay the UPSAMPLED extents.  They may be odd:
+ *   that is F.interpolate(size=(2n - 1, ...)), the nearest-2x image with its last row / column cropped, and the conv pads with
+ *   zeros at the cropped edge.  Even extents are F.interpolate(scale_factor=2).  az_conv2d_wgrad_bias_bf16 takes the same flag
+ *   as ksize | 16.
  * ldx / lddy / ldo / ldr: elements between consecutive pixels.  Cin multiple of 8. */
 /* ref: train.py:2760-2761 / 2765 (every nn.Conv2d of ResnetBlock2D, Downsample2D, Upsample2D, conv_in, conv_out and its backward) */
 int az_conv2d_bf16(int mode, int batch, int Hin, int Win, int Cin, int Hout, int Wout, int Cout, int ksize, int stride,
@@ -261,6 +263,15 @@ int az_add_rows(long rows, int C, const void* a, long lda, const void* b, long l
 int az_upsample2x_fwd(int batch, int H, int W, int C, const void* x, void* y, void* stream);
 /* ref: train.py:2765 (its autograd) */
 int az_upsample2x_bwd(int batch, int H, int W, int C, const void* dy, void* dx, void* stream);
+/* nearest-neighbour upsample NHWC x[B][H][W][C] -> y[B][Hout][Wout][C] to a target size, Hout in {2H - 1, 2H}, Wout in {2W - 1, 2W}
+ * (anything else is an argument error): y[oy][ox] = x[oy >> 1][ox >> 1], which is what F.interpolate(size=, mode="nearest")
+ * computes for these targets -- the 2x image with its last row / column cropped.  The adjoint is the 2x2 fold in which a source
+ * pixel on a cropped edge receives 2 or 1 contributions instead of 4 (fp32 sums, rounded once).  C multiple of 8. */
+/* ref: train.py:2760-2761 (Upsample2D with output_size: F.interpolate(size=upsample_size, mode="nearest"), taken by diffusers
+ *      UNet2DConditionModel.forward when a sample side is not a multiple of 2**num_upsamplers) */
+int az_upsample_nearest_fwd(int batch, int H, int W, int Hout, int Wout, int C, const void* x, void* y, void* stream);
+/* ref: train.py:2765 (its autograd) */
+int az_upsample_nearest_bwd(int batch, int H, int W, int Hout, int Wout, int C, const void* dy, void* dx, void* stream);
 /* out[seg][C] fp32 = column sums of x[seg*rows_per_seg ...][C] (bias / time-embedding grads); two ordered
  * passes through scratch_f32 (>= az_colsum_scratch_floats), no atomics: bitwise reproducible */
 /* ref: no reference counterpart (workspace size query) */
