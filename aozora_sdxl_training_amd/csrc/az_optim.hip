@@ -5,6 +5,7 @@
 #include "aozora_hip.h"
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 namespace {
 
@@ -16,13 +17,15 @@ template <typename T> __device__ __forceinline__ float ldf(const T* p, long i);
 template <> __device__ __forceinline__ float ldf<bf16_t>(const bf16_t* p, long i) { return bf2f(p[i]); }
 template <> __device__ __forceinline__ float ldf<float>(const float* p, long i) { return p[i]; }
 template <> __device__ __forceinline__ float ldf<f16_t>(const f16_t* p, long i) { return (float)p[i]; }
-template <typename T> __device__ __forceinline__ void stf(T* p, long i, float v);
+// value of a moment as it is stored: the fp32 value rounded to the moment type
+template <typename T> __device__ __forceinline__ T cvt_moment(float v);
 // fp16 moments store the fp32 value rounded once more, as the reference's `.to(float16)` of an fp32 tensor does.  The empty asm hides
 // where v came from: left alone the compiler folds the fused multiply-add behind exp_avg into v_fma_mixlo_f16, ONE rounding of the
 // exact a * b + c to fp16 -- a different fp16 neighbour on 0.4 % of the elements (tests/test_elem_gpu.py, mdtype 2).
-template <> __device__ __forceinline__ void stf<f16_t>(f16_t* p, long i, float v) { asm volatile("" : "+v"(v)); p[i] = (f16_t)v; }
-template <> __device__ __forceinline__ void stf<bf16_t>(bf16_t* p, long i, float v) { p[i] = f2bf(v); }
-template <> __device__ __forceinline__ void stf<float>(float* p, long i, float v) { p[i] = v; }
+template <> __device__ __forceinline__ f16_t cvt_moment<f16_t>(float v) { asm volatile("" : "+v"(v)); return (f16_t)v; }
+template <> __device__ __forceinline__ bf16_t cvt_moment<bf16_t>(float v) { return f2bf(v); }
+template <> __device__ __forceinline__ float cvt_moment<float>(float v) { return v; }
+template <typename T> __device__ __forceinline__ void stf(T* p, long i, float v) { p[i] = cvt_moment<T>(v); }
 
 template <typename T>
 __global__ void sumsq_partial_kernel(long n, const T* __restrict__ g, float* __restrict__ partial) {
@@ -74,30 +77,162 @@ __global__ void clip_coef_kernel(const float* sumsq, float max_norm, float unsca
   }
 }
 
+// ---- stochastic rounding of the bf16 parameter write (an option the reference does not have: INTEGRATION.md) -------------------------
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11) in plain integer arithmetic: counter-based, so
+// the bits of an element are a function of (seed, optimizer step, domain, GLOBAL element index) and of nothing else -- not of how the
+// flat range is cut into launches, chunks, regions or rank shards.
+struct SrArgs {
+  uint32_t k0, k1;     // key: seed low / high word
+  uint32_t step, dom;  // counter words 2, 3
+  long elem0;          // global index of the call's first element; counter words 0, 1 = (elem0 + i) >> 3
+  long head, groups;   // [0, head) scalar, then `groups` aligned groups of 8 (16-byte accesses), then the scalar tail up to n
+};
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+__device__ __forceinline__ void sr_group_bits(const SrArgs& sr, long group, uint32_t* w) {
+  philox4x32_10((uint32_t)group, (uint32_t)((unsigned long)group >> 32), sr.step, sr.dom, sr.k0, sr.k1, w);
+}
+// 16 bits for the element in lane `l` (= e & 7) of its group: word l >> 1, low half for even l
+__device__ __forceinline__ uint32_t sr_lane_bits(const uint32_t* w, int l) { return (w[l >> 1] >> ((l & 1) << 4)) & 0xFFFFu; }
+
+// fp32 -> bf16 bits, rounding the MAGNITUDE up with probability (low half) / 65536: r is uniform in [0, 65536).  Non-finite values and a
+// carry into the all-ones exponent (a finite value never becomes inf) keep today's behaviour / truncate.
+__device__ __forceinline__ bf16_t sr_round(float pp, uint32_t r) {
+  const uint32_t u = __float_as_uint(pp);
+  if ((u & 0x7F800000u) == 0x7F800000u) return f2bf(pp);
+  uint32_t o = (u + r) >> 16;
+  if ((o & 0x7F80u) == 0x7F80u) o = u >> 16;
+  return (bf16_t)o;
+}
+
+struct AdamwK { float b1, b2, eps, wdf, step, sbc2, gc, omb1, omb2; };
+
+__device__ __forceinline__ AdamwK adamw_consts(const float* __restrict__ hyper, const float* __restrict__ coef) {
+  AdamwK k;
+  k.b1 = hyper[1]; k.b2 = hyper[2]; k.eps = hyper[3]; k.wdf = hyper[4]; k.step = hyper[5]; k.sbc2 = hyper[6];
+  k.gc = coef ? coef[0] : 1.0f;
+  k.omb1 = 1.0f - k.b1; k.omb2 = 1.0f - k.b2;
+  return k;
+}
+
+// One element of the update: reads its four inputs through the callables ldg / ldm / ldv / ldp (memory in the scalar form, registers
+// in the 8-wide form -- read where the original kernel read them, so the scalar form compiles to the instruction stream it always had)
+// and leaves the new fp32 values: mm, vv still to be rounded to the moment type, pp to bf16 (the ONE place where the forms differ).
+template <typename TG, typename LG, typename LM, typename LV, typename LP>
+__device__ __forceinline__ void adamw_math(const AdamwK& k, LG ldg, LM ldm, LV ldv, LP ldp, float& mm, float& vv, float& pp) {
+  // The reference's operation order (raven.py:125-143, fp32 scratch tensors), rounding for rounding -- this TU's default
+  // contraction would fuse differently and the update is host-link-bound, so the extra roundings cost nothing:
+  //   exp_avg.mul_(b1).add_(g, alpha=1-b1)            ATen's add-with-alpha is a fused multiply-add (vec::fmadd)
+  //   exp_avg_sq.mul_(b2).addcmul_(g, g, value=1-b2)  self + ((value * g) * g), each product and the sum rounded
+  //   p.mul_(wd_factor); denom = sqrt(v) / sqrt_bc2 + eps; p.addcdiv_(m, denom, value=-step_size)   self + ((value * m) / denom)
+#pragma clang fp contract(off)
+  float gr = ldg() * k.gc;
+  if constexpr (sizeof(TG) == 2) gr = bf2f(f2bf(gr));   // = reading a gradient that was clipped in place (bf16 rounding)
+  mm = ldm() * k.b1; mm = __builtin_fmaf(gr, k.omb1, mm);
+  vv = ldv() * k.b2; vv = vv + ((k.omb2 * gr) * gr);
+  pp = ldp() * k.wdf;
+  const float denom = sqrtf(vv) / k.sbc2 + k.eps;
+  pp = pp + ((-k.step * mm) / denom);
+}
+
+// Element i of the range through memory.  SR: r16 = the element's 16 random bits; otherwise round to nearest even (raven.py:144).
+template <typename TM, typename TG, bool SR>
+__device__ __forceinline__ void adamw_elem(const AdamwK& k, long i, bf16_t* __restrict__ p, const TG* __restrict__ g, TM* __restrict__ m,
+                                           TM* __restrict__ v, uint32_t r16) {
+  float mm, vv, pp;
+  adamw_math<TG>(k, [&] { return ldf<TG>(g, i); }, [&] { return ldf<TM>(m, i); }, [&] { return ldf<TM>(v, i); }, [&] { return bf2f(p[i]); },
+                 mm, vv, pp);
+  if constexpr (SR) p[i] = sr_round(pp, r16); else p[i] = f2bf(pp);
+  stf<TM>(m, i, mm);
+  stf<TM>(v, i, vv);
+}
+
+// 8 consecutive elements <-> registers with 16-byte accesses (the pointer is 16-byte aligned: launch_adamw_sr)
+template <typename T> __device__ __forceinline__ void load8(const T* __restrict__ q, float* x) {
+  if constexpr (sizeof(T) == 4) {
+    const float4 a = reinterpret_cast<const float4*>(q)[0], b = reinterpret_cast<const float4*>(q)[1];
+    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+  } else {
+    const uint4 u = reinterpret_cast<const uint4*>(q)[0];
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if constexpr (std::is_same<T, f16_t>::value) {
+        x[2 * e] = (float)__builtin_bit_cast(f16_t, (uint16_t)(w[e] & 0xFFFFu));
+        x[2 * e + 1] = (float)__builtin_bit_cast(f16_t, (uint16_t)(w[e] >> 16));
+      } else {
+        x[2 * e] = __uint_as_float(w[e] << 16);
+        x[2 * e + 1] = __uint_as_float(w[e] & 0xFFFF0000u);
+      }
+    }
+  }
+}
+template <typename T> __device__ __forceinline__ void store8_moment(T* __restrict__ q, const float* x) {
+  if constexpr (sizeof(T) == 4) {
+    reinterpret_cast<float4*>(q)[0] = make_float4(x[0], x[1], x[2], x[3]);
+    reinterpret_cast<float4*>(q)[1] = make_float4(x[4], x[5], x[6], x[7]);
+  } else {
+    uint32_t w[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      w[e] = (uint32_t)__builtin_bit_cast(uint16_t, cvt_moment<T>(x[2 * e])) | ((uint32_t)__builtin_bit_cast(uint16_t, cvt_moment<T>(x[2 * e + 1])) << 16);
+    reinterpret_cast<uint4*>(q)[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+
 // hyper: [0] lr (unused here) [1] beta1 [2] beta2 [3] eps [4] wd_factor [5] step_size [6] sqrt_bc2
+// (the grid-stride loops stay in the kernels themselves: blockDim / gridDim read from an inlined device function take the slow path)
 template <typename TM, typename TG>
 __global__ void adamw_kernel(long n, bf16_t* __restrict__ p, const TG* __restrict__ g, TM* __restrict__ m, TM* __restrict__ v,
                              const float* __restrict__ hyper, const float* __restrict__ coef) {
-  const float b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wdf = hyper[4], step = hyper[5], sbc2 = hyper[6];
-  const float gc = coef ? coef[0] : 1.0f;
-  const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    // The reference's operation order (raven.py:125-143, fp32 scratch tensors), rounding for rounding -- this TU's default
-    // contraction would fuse differently and the update is host-link-bound, so the extra roundings cost nothing:
-    //   exp_avg.mul_(b1).add_(g, alpha=1-b1)            ATen's add-with-alpha is a fused multiply-add (vec::fmadd)
-    //   exp_avg_sq.mul_(b2).addcmul_(g, g, value=1-b2)  self + ((value * g) * g), each product and the sum rounded
-    //   p.mul_(wd_factor); denom = sqrt(v) / sqrt_bc2 + eps; p.addcdiv_(m, denom, value=-step_size)   self + ((value * m) / denom)
-#pragma clang fp contract(off)
-    float gr = ldf<TG>(g, i) * gc;
-    if constexpr (sizeof(TG) == 2) gr = bf2f(f2bf(gr));   // = reading a gradient that was clipped in place (bf16 rounding)
-    float mm = ldf<TM>(m, i) * b1; mm = __builtin_fmaf(gr, omb1, mm);
-    float vv = ldf<TM>(v, i) * b2; vv = vv + ((omb2 * gr) * gr);
-    float pp = bf2f(p[i]) * wdf;
-    const float denom = sqrtf(vv) / sbc2 + eps;
-    pp = pp + ((-step * mm) / denom);
-    p[i] = f2bf(pp);
-    stf<TM>(m, i, mm);
-    stf<TM>(v, i, vv);
+  const AdamwK k = adamw_consts(hyper, coef);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    adamw_elem<TM, TG, false>(k, i, p, g, m, v, 0u);
+}
+
+// az_adamw_flat_sr: the same element update, p written with stochastic rounding.  One thread per aligned group of 8 elements (one
+// Philox evaluation, 16-byte accesses to p, g, m, v); the scalar head [0, head) and the tail behind the last whole group evaluate
+// their group's Philox word per element.
+template <typename TM, typename TG>
+__global__ void adamw_sr_kernel(long n, bf16_t* __restrict__ p, const TG* __restrict__ g, TM* __restrict__ m, TM* __restrict__ v,
+                                const float* __restrict__ hyper, const float* __restrict__ coef, SrArgs sr) {
+  const AdamwK k = adamw_consts(hyper, coef);
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long)gridDim.x * blockDim.x;
+  const long body = sr.head + (sr.groups << 3);             // <= n (launch_adamw_sr)
+  for (long gi = tid; gi < sr.groups; gi += nthr) {
+    const long i = sr.head + (gi << 3);                     // (elem0 + i) & 7 == 0
+    uint32_t w[4];
+    sr_group_bits(sr, (sr.elem0 + i) >> 3, w);
+    float gg[8], mm[8], vv[8], pp[8];
+    load8<TG>(g + i, gg); load8<TM>(m + i, mm); load8<TM>(v + i, vv); load8<bf16_t>(p + i, pp);
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      adamw_math<TG>(k, [&] { return gg[e]; }, [&] { return mm[e]; }, [&] { return vv[e]; }, [&] { return pp[e]; }, mm[e], vv[e], pp[e]);
+    uint32_t o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      o[e] = (uint32_t)sr_round(pp[2 * e], w[e] & 0xFFFFu) | ((uint32_t)sr_round(pp[2 * e + 1], w[e] >> 16) << 16);
+    reinterpret_cast<uint4*>(p + i)[0] = make_uint4(o[0], o[1], o[2], o[3]);
+    store8_moment<TM>(m + i, mm);
+    store8_moment<TM>(v + i, vv);
+  }
+  const long nscalar = n - (sr.groups << 3);                 // head + tail
+  for (long j = tid; j < nscalar; j += nthr) {
+    const long i = j < sr.head ? j : j - sr.head + body;
+    const long e = sr.elem0 + i;
+    uint32_t w[4];
+    sr_group_bits(sr, e >> 3, w);
+    adamw_elem<TM, TG, true>(k, i, p, g, m, v, sr_lane_bits(w, (int)(e & 7)));
   }
 }
 
@@ -151,6 +286,40 @@ int launch_adamw(long n, void* p, const void* g, int gdtype, void* m, void* v, i
   return AZ_OK;
 }
 
+// Stochastic-rounding form.  The vector body needs (elem0 + i) % 8 == 0 AND 16-byte aligned p, g, m, v at the same i: true whenever the
+// range starts on an owner's flat buffer (elem0 is then the offset in it); otherwise every element takes the scalar path.
+int launch_adamw_sr(long n, void* p, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper, const void* coef,
+                    long seed, long step, long domain, long elem0, hipStream_t st) {
+  if (mdtype < 0 || mdtype > 2 || gdtype < 0 || gdtype > 1 || elem0 < 0) return AZ_ERR_ARG(68);
+  const size_t esz = mdtype == 1 ? 4 : 2, gsz = gdtype == 0 ? 2 : 4;
+  SrArgs sr;
+  sr.k0 = (uint32_t)(unsigned long)seed; sr.k1 = (uint32_t)((unsigned long)seed >> 32);
+  sr.step = (uint32_t)step; sr.dom = (uint32_t)domain; sr.elem0 = elem0;
+  long head = (8 - (elem0 & 7)) & 7;
+  if (head > n) head = n;
+  const bool aligned = (((uintptr_t)p + head * 2) & 15) == 0 && (((uintptr_t)g + head * gsz) & 15) == 0 &&
+                       (((uintptr_t)m + head * esz) & 15) == 0 && (((uintptr_t)v + head * esz) & 15) == 0;
+  if (!aligned) head = n;
+  sr.head = head; sr.groups = (n - head) >> 3;
+  const long nscalar = n - (sr.groups << 3);
+  dim3 grid(grid_for((sr.groups > nscalar ? sr.groups : nscalar))), blk(256);
+  const float* hy = (const float*)hyper; const float* cf = (const float*)coef;
+  if (mdtype == 0 && gdtype == 0)
+    az_launch((adamw_sr_kernel<bf16_t, bf16_t>), grid, blk, 0, st, n, (bf16_t*)p, (const bf16_t*)g, (bf16_t*)m, (bf16_t*)v, hy, cf, sr);
+  else if (mdtype == 1 && gdtype == 0)
+    az_launch((adamw_sr_kernel<float, bf16_t>), grid, blk, 0, st, n, (bf16_t*)p, (const bf16_t*)g, (float*)m, (float*)v, hy, cf, sr);
+  else if (mdtype == 0 && gdtype == 1)
+    az_launch((adamw_sr_kernel<bf16_t, float>), grid, blk, 0, st, n, (bf16_t*)p, (const float*)g, (bf16_t*)m, (bf16_t*)v, hy, cf, sr);
+  else if (mdtype == 1 && gdtype == 1)
+    az_launch((adamw_sr_kernel<float, float>), grid, blk, 0, st, n, (bf16_t*)p, (const float*)g, (float*)m, (float*)v, hy, cf, sr);
+  else if (mdtype == 2 && gdtype == 0)
+    az_launch((adamw_sr_kernel<f16_t, bf16_t>), grid, blk, 0, st, n, (bf16_t*)p, (const bf16_t*)g, (f16_t*)m, (f16_t*)v, hy, cf, sr);
+  else
+    az_launch((adamw_sr_kernel<f16_t, float>), grid, blk, 0, st, n, (bf16_t*)p, (const float*)g, (f16_t*)m, (f16_t*)v, hy, cf, sr);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+
 // Hand-off events of the chunk pipeline, one set per COMPUTE STREAM (a stream belongs to one device, so two optimizers,
 // threads or devices in one process never share a set); creation is serialised by a mutex.  Calls that name the same
 // compute stream must come from one host thread at a time -- the stream's own order is what sequences them.
@@ -173,6 +342,53 @@ int ev_pool_for(hipStream_t sc, EvPool** out) {
     it = g_ev_pools.emplace(sc, ep).first;
   }
   *out = &it->second;
+  return AZ_OK;
+}
+
+struct SrCall { long seed, step, domain, elem0; };
+
+// Chunk pipeline: H2D(m,v)[c+1]  ||  adamw[c]  ||  D2H(m,v)[c-1]; staging = 2 buffers x (m,v) x chunk.  sr: stochastic rounding, each
+// chunk's launch names the global index of ITS first element (elem0 + chunk offset).
+int raven_pipeline(long n, void* p, const void* g, int gdtype, void* m_host, void* v_host, int mdtype, const void* hyper,
+                   const void* coef, void* staging, long chunk_elems, void* stream_compute, void* stream_h2d,
+                   void* stream_d2h, const SrCall* sr) {
+  if (n <= 0 || chunk_elems <= 0 || mdtype < 0 || mdtype > 2) return AZ_ERR_ARG(64);
+  hipStream_t sc = (hipStream_t)stream_compute, sh = (hipStream_t)stream_h2d, sd = (hipStream_t)stream_d2h;
+  EvPool* evp = nullptr;
+  { int rc0 = ev_pool_for(sc, &evp); if (rc0) return rc0; }
+  EvPool& g_ev = *evp;
+  const size_t esz = mdtype == 1 ? 4 : 2;
+  const size_t gsz = gdtype == 0 ? 2 : 4;
+  char* stg = (char*)staging;
+  const long nchunk = (n + chunk_elems - 1) / chunk_elems;
+  // the copy streams must not start before work already queued on the compute stream (grads, coef)
+  hipEvent_t& start = g_ev.comp[0];
+  AZ_HIP(hipEventRecord(start, sc));
+  AZ_HIP(hipStreamWaitEvent(sh, start, 0));
+  for (long c = 0; c < nchunk; ++c) {
+    const int buf = (int)(c & 1);
+    const long off = c * chunk_elems;
+    const long len = (off + chunk_elems <= n) ? chunk_elems : (n - off);
+    char* mb = stg + (size_t)buf * 2 * chunk_elems * esz;
+    char* vb = mb + (size_t)chunk_elems * esz;
+    if (c >= 2) AZ_HIP(hipStreamWaitEvent(sh, g_ev.d2h[buf], 0));       // staging buffer free again
+    AZ_HIP(hipMemcpyAsync(mb, (char*)m_host + off * esz, len * esz, hipMemcpyHostToDevice, sh));
+    AZ_HIP(hipMemcpyAsync(vb, (char*)v_host + off * esz, len * esz, hipMemcpyHostToDevice, sh));
+    AZ_HIP(hipEventRecord(g_ev.h2d[buf], sh));
+    AZ_HIP(hipStreamWaitEvent(sc, g_ev.h2d[buf], 0));
+    int rc = sr ? launch_adamw_sr(len, (bf16_t*)p + off, (const char*)g + off * gsz, gdtype, mb, vb, mdtype, hyper, coef, sr->seed, sr->step,
+                                  sr->domain, sr->elem0 + off, sc)
+                : launch_adamw(len, (bf16_t*)p + off, (const char*)g + off * gsz, gdtype, mb, vb, mdtype, hyper, coef, sc);
+    if (rc) return rc;
+    AZ_HIP(hipEventRecord(g_ev.comp[buf], sc));
+    AZ_HIP(hipStreamWaitEvent(sd, g_ev.comp[buf], 0));
+    AZ_HIP(hipMemcpyAsync((char*)m_host + off * esz, mb, len * esz, hipMemcpyDeviceToHost, sd));
+    AZ_HIP(hipMemcpyAsync((char*)v_host + off * esz, vb, len * esz, hipMemcpyDeviceToHost, sd));
+    AZ_HIP(hipEventRecord(g_ev.d2h[buf], sd));
+  }
+  // join: the compute stream observes the end of the last write-backs
+  AZ_HIP(hipStreamWaitEvent(sc, g_ev.d2h[0], 0));
+  if (nchunk > 1) AZ_HIP(hipStreamWaitEvent(sc, g_ev.d2h[1], 0));
   return AZ_OK;
 }
 
@@ -219,48 +435,27 @@ int az_adamw_flat_ex(long n, void* p, const void* g, int gdtype, void* m, void* 
   return launch_adamw(n, p, g, gdtype, m, v, mdtype, hyper, coef, (hipStream_t)stream);
 }
 
-// Chunk pipeline: H2D(m,v)[c+1]  ||  adamw[c]  ||  D2H(m,v)[c-1]; staging = 2 buffers x (m,v) x chunk.
+int az_adamw_flat_sr(long n, void* p, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper, const void* coef,
+                     long seed, long step, long domain, long elem0, void* stream) {
+  if (n <= 0) return AZ_ERR_ARG(63);
+  return launch_adamw_sr(n, p, g, gdtype, m, v, mdtype, hyper, coef, seed, step, domain, elem0, (hipStream_t)stream);
+}
+
 int az_raven_step_ex(long n, void* p, const void* g, int gdtype, void* m_host, void* v_host, int mdtype, const void* hyper,
                      const void* coef, void* staging, long chunk_elems, void* stream_compute, void* stream_h2d,
                      void* stream_d2h) {
-  if (n <= 0 || chunk_elems <= 0 || mdtype < 0 || mdtype > 2) return AZ_ERR_ARG(64);
-  hipStream_t sc = (hipStream_t)stream_compute, sh = (hipStream_t)stream_h2d, sd = (hipStream_t)stream_d2h;
-  EvPool* evp = nullptr;
-  { int rc0 = ev_pool_for(sc, &evp); if (rc0) return rc0; }
-  EvPool& g_ev = *evp;
-  const size_t esz = mdtype == 1 ? 4 : 2;
-  const size_t gsz = gdtype == 0 ? 2 : 4;
-  char* stg = (char*)staging;
-  const long nchunk = (n + chunk_elems - 1) / chunk_elems;
-  // the copy streams must not start before work already queued on the compute stream (grads, coef)
-  hipEvent_t& start = g_ev.comp[0];
-  AZ_HIP(hipEventRecord(start, sc));
-  AZ_HIP(hipStreamWaitEvent(sh, start, 0));
-  for (long c = 0; c < nchunk; ++c) {
-    const int buf = (int)(c & 1);
-    const long off = c * chunk_elems;
-    const long len = (off + chunk_elems <= n) ? chunk_elems : (n - off);
-    char* mb = stg + (size_t)buf * 2 * chunk_elems * esz;
-    char* vb = mb + (size_t)chunk_elems * esz;
-    if (c >= 2) AZ_HIP(hipStreamWaitEvent(sh, g_ev.d2h[buf], 0));       // staging buffer free again
-    AZ_HIP(hipMemcpyAsync(mb, (char*)m_host + off * esz, len * esz, hipMemcpyHostToDevice, sh));
-    AZ_HIP(hipMemcpyAsync(vb, (char*)v_host + off * esz, len * esz, hipMemcpyHostToDevice, sh));
-    AZ_HIP(hipEventRecord(g_ev.h2d[buf], sh));
-    AZ_HIP(hipStreamWaitEvent(sc, g_ev.h2d[buf], 0));
-    int rc = launch_adamw(len, (bf16_t*)p + off, (const char*)g + off * gsz, gdtype, mb, vb, mdtype, hyper, coef, sc);
-    if (rc) return rc;
-    AZ_HIP(hipEventRecord(g_ev.comp[buf], sc));
-    AZ_HIP(hipStreamWaitEvent(sd, g_ev.comp[buf], 0));
-    AZ_HIP(hipMemcpyAsync((char*)m_host + off * esz, mb, len * esz, hipMemcpyDeviceToHost, sd));
-    AZ_HIP(hipMemcpyAsync((char*)v_host + off * esz, vb, len * esz, hipMemcpyDeviceToHost, sd));
-    AZ_HIP(hipEventRecord(g_ev.d2h[buf], sd));
-  }
-  // join: the compute stream observes the end of the last write-backs
-  AZ_HIP(hipStreamWaitEvent(sc, g_ev.d2h[0], 0));
-  if (nchunk > 1) AZ_HIP(hipStreamWaitEvent(sc, g_ev.d2h[1], 0));
-  return AZ_OK;
+  return raven_pipeline(n, p, g, gdtype, m_host, v_host, mdtype, hyper, coef, staging, chunk_elems, stream_compute, stream_h2d, stream_d2h,
+                        nullptr);
 }
 
+int az_raven_step_sr(long n, void* p, const void* g, int gdtype, void* m_host, void* v_host, int mdtype, const void* hyper,
+                     const void* coef, void* staging, long chunk_elems, void* stream_compute, void* stream_h2d,
+                     void* stream_d2h, long seed, long step, long domain, long elem0) {
+  if (gdtype < 0 || gdtype > 1 || elem0 < 0) return AZ_ERR_ARG(64);
+  const SrCall sr = {seed, step, domain, elem0};
+  return raven_pipeline(n, p, g, gdtype, m_host, v_host, mdtype, hyper, coef, staging, chunk_elems, stream_compute, stream_h2d, stream_d2h,
+                        &sr);
+}
 int az_raven_step(long n, void* p, const void* g, void* m_host, void* v_host, int mdtype, const void* hyper,
                   const void* coef, void* staging, long chunk_elems, void* stream_compute, void* stream_h2d,
                   void* stream_d2h) {

@@ -104,9 +104,14 @@ class ShardedRaven:
 
     def __init__(self, unet, lr=8e-7, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, debias_strength=0.3,
                  momentum_dtype=torch.bfloat16, clip_grad_norm=1.0, process_group=None, force_local=False,
-                 overlap=True, regions: Optional[int] = None, force_exchange=False, state_on_host=False):
+                 overlap=True, regions: Optional[int] = None, force_exchange=False, state_on_host=False,
+                 stochastic_rounding: bool = False, sr_seed: int = 0):
         import torch.distributed as dist
         self.unet = unet
+        # stochastic rounding of the bf16 write-back (not in the reference, off by default: optimizers.RavenAdamW): the random bits are
+        # keyed by (sr_seed, step_count, offset in the flat buffer), so regions, rank shards and RavenAdamW's ranges all draw the same
+        self.sr = bool(stochastic_rounding)
+        self.sr_seed = int(sr_seed)
         self.state_on_host = bool(state_on_host)
         self.dist = dist if (dist.is_available() and dist.is_initialized() and not force_local) else None
         self.pg = process_group
@@ -327,6 +332,12 @@ class ShardedRaven:
             sp = ctypes.c_void_p(stream.cuda_stream)
             for k, (a, b) in enumerate(self.ranges[i]):
                 hoff = self.range_off[i][k]
+                if self.sr:
+                    L.call("az_adamw_flat_sr", b - a, ctypes.c_void_p(u.pflat.data_ptr() + a * 2), ctypes.c_void_p(u.gflat.data_ptr() + a * 2), 0,
+                           ctypes.c_void_p(self.m_dev.data_ptr() + hoff * esz), ctypes.c_void_p(self.v_dev.data_ptr() + hoff * esz),
+                           _MD[self.mdt], ctypes.c_void_p(self.hyper_dev.data_ptr()), ctypes.c_void_p(self.scal[1:2].data_ptr()),
+                           self.sr_seed, self.step_count, 0, a, sp)
+                    continue
                 L.call("az_adamw_flat", b - a, ctypes.c_void_p(u.pflat.data_ptr() + a * 2), ctypes.c_void_p(u.gflat.data_ptr() + a * 2),
                        ctypes.c_void_p(self.m_dev.data_ptr() + hoff * esz), ctypes.c_void_p(self.v_dev.data_ptr() + hoff * esz),
                        _MD[self.mdt], ctypes.c_void_p(self.hyper_dev.data_ptr()), ctypes.c_void_p(self.scal[1:2].data_ptr()), sp)   # clip coefficient applied in-kernel
@@ -686,6 +697,12 @@ class ShardedTitan(ShardedRaven):
         for i, rs in enumerate(self.ranges):
             for k, (a, b) in enumerate(rs):
                 hoff = self.range_off[i][k]
+                if self.sr:
+                    L.call("az_adamw_flat_sr", b - a, ctypes.c_void_p(u.pflat.data_ptr() + a * 2), ctypes.c_void_p(self.gacc.data_ptr() + a * 4), 1,
+                           ctypes.c_void_p(self.m_dev.data_ptr() + hoff * esz), ctypes.c_void_p(self.v_dev.data_ptr() + hoff * esz),
+                           _MD[self.mdt], ctypes.c_void_p(self.hyper_dev.data_ptr()), ctypes.c_void_p(self.scal[1:2].data_ptr()),
+                           self.sr_seed, self.step_count, 0, a, st)
+                    continue
                 L.call("az_adamw_flat_ex", b - a, ctypes.c_void_p(u.pflat.data_ptr() + a * 2), ctypes.c_void_p(self.gacc.data_ptr() + a * 4), 1,
                        ctypes.c_void_p(self.m_dev.data_ptr() + hoff * esz), ctypes.c_void_p(self.v_dev.data_ptr() + hoff * esz),
                        _MD[self.mdt], ctypes.c_void_p(self.hyper_dev.data_ptr()), ctypes.c_void_p(self.scal[1:2].data_ptr()), st)

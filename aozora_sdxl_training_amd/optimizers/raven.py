@@ -55,11 +55,17 @@ class RavenAdamW(Optimizer):
     _GRAD_SOURCE = "device"
 
     def __init__(self, params, lr: float = 1e-4, betas=(0.9, 0.98), weight_decay: float = 0.06, eps: float = 1e-8,
-                 debias_strength: float = 0.9, momentum_dtype: torch.dtype = torch.bfloat16, state_on_device: bool = False):
+                 debias_strength: float = 0.9, momentum_dtype: torch.dtype = torch.bfloat16, state_on_device: bool = False,
+                 stochastic_rounding: bool = False, sr_seed: int = 0):
         """state_on_device (not in the reference): keep exp_avg / exp_avg_sq resident in device memory instead of pinned host memory
         streamed through staging buffers every step (raven.py:83-84, 114-117: the reference's way onto 24 GB cards; 10.3 GB for
         SDXL-base in bf16).  Same kernel arithmetic on the same values: bit-identical parameters; `state[p]["exp_avg"]` is then a
-        device tensor, save_cpu_state() / load_cpu_state() still speak the reference's CPU layout."""
+        device tensor, save_cpu_state() / load_cpu_state() still speak the reference's CPU layout.
+
+        stochastic_rounding (not in the reference, off by default): write the fp32 result to the bf16 parameter with stochastic
+        rounding instead of round-to-nearest-even (raven.py:144), which at small learning rates discards almost the whole update
+        (INTEGRATION.md).  The random bits are a function of (sr_seed, the parameter's step count, its position, the element index),
+        so a run repeats bit for bit and resumes from its checkpoint; the option SELECTS results: they differ from the default's."""
         if not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr}")
         valid = [torch.float32, torch.float16, torch.bfloat16]
@@ -70,6 +76,8 @@ class RavenAdamW(Optimizer):
         super().__init__(params, defaults)
         self._momentum_dtype = momentum_dtype
         self._state_on_device = bool(state_on_device)
+        self._sr = bool(stochastic_rounding)
+        self._sr_seed = int(sr_seed)
         if self._state_on_device and self._GDTYPE != 0:
             raise AozoraError("state_on_device needs device gradients (RavenAdamW); TitanAdamW keeps its gradients in host memory -- use dist.ShardedTitan")
         self.max_numel = 0
@@ -166,13 +174,15 @@ class RavenAdamW(Optimizer):
             with torch.enable_grad():
                 loss = closure()
         self._ensure_runtime()
-        segs: List[list] = []   # [p_ptr, g_ptr, host_key, host_off, numel, hyper-tuple]
+        segs: List[list] = []   # [p_ptr, g_ptr, host_key, host_off, numel, hyper-tuple, (step, domain) of stochastic rounding]
+        pos = 0                 # position in parameter order
         for group in self.param_groups:
             lr = group["lr"]
             beta1, beta2 = group["betas"]
             wd, eps, debias = group["weight_decay"], group["eps"], group["debias_strength"]
             wd_factor = 1.0 - lr * wd if wd != 0 else 1.0
             for p in group["params"]:
+                pos += 1
                 gptr = self._grad_ptr(p)
                 if gptr is None:
                     continue
@@ -189,12 +199,15 @@ class RavenAdamW(Optimizer):
                 hyper = (lr, beta1, beta2, eps, wd_factor, lr / bc1, math.sqrt(bc2), 0.0)
                 pptr, n, _ = _storage_span(p)
                 key, hoff, _ = self._spans[p]
+                # stochastic rounding: domain 0 and the offset in the owner's flat buffer (= hoff) name an AozoraUNet element, domain
+                # 1 + position and the offset in the tensor a foreign one; ranges merge only under one (step, domain)
+                srk = (step, 0 if getattr(p, "_az_owner", None) is not None else pos) if self._sr else None
                 last = segs[-1] if segs else None
                 if (last is not None and last[5] == hyper and last[2] is key and last[0] + last[4] * 2 == pptr
-                        and last[1] + last[4] * self._GSIZE == gptr and last[3] + last[4] == hoff):
+                        and last[1] + last[4] * self._GSIZE == gptr and last[3] + last[4] == hoff and last[6] == srk):
                     last[4] += n
                 else:
-                    segs.append([pptr, gptr, key, hoff, n, hyper])
+                    segs.append([pptr, gptr, key, hoff, n, hyper, srk])
         if not segs:
             return loss
         if len(segs) > self._hyper_host.shape[0]:
@@ -212,8 +225,23 @@ class RavenAdamW(Optimizer):
         esz = 4 if self._momentum_dtype == torch.float32 else 2
         coef = self.clip_coef if self.clip_coef is not None else None
         L = lib()
-        for i, (pptr, gptr, key, hoff, n, _) in enumerate(segs):
+        for i, (pptr, gptr, key, hoff, n, _, srk) in enumerate(segs):
             hs = self._host[key]
+            if srk is not None:               # the same two calls with the bf16 write-back stochastically rounded
+                sr = (self._sr_seed, srk[0], srk[1], hoff)
+                if self._state_on_device:
+                    L.call("az_adamw_flat_sr", n, ctypes.c_void_p(pptr), ctypes.c_void_p(gptr), self._GDTYPE,
+                           ctypes.c_void_p(hs.m.data_ptr() + hoff * esz), ctypes.c_void_p(hs.v.data_ptr() + hoff * esz),
+                           _MD[self._momentum_dtype], ctypes.c_void_p(self._hyper_dev[i].data_ptr()),
+                           ctypes.c_void_p(coef.data_ptr() if coef is not None else 0), *sr, ctypes.c_void_p(sc.cuda_stream))
+                    continue
+                L.call("az_raven_step_sr", n, ctypes.c_void_p(pptr), ctypes.c_void_p(gptr), self._GDTYPE,
+                       ctypes.c_void_p(hs.m.data_ptr() + hoff * esz), ctypes.c_void_p(hs.v.data_ptr() + hoff * esz),
+                       _MD[self._momentum_dtype], ctypes.c_void_p(self._hyper_dev[i].data_ptr()),
+                       ctypes.c_void_p(coef.data_ptr() if coef is not None else 0), ctypes.c_void_p(self._staging.data_ptr()),
+                       CHUNK_ELEMS, ctypes.c_void_p(sc.cuda_stream), ctypes.c_void_p(self._copy_streams[0].cuda_stream),
+                       ctypes.c_void_p(self._copy_streams[1].cuda_stream), *sr)
+                continue
             if self._state_on_device:          # resident moments: the update kernel alone, on the compute stream
                 L.call("az_adamw_flat_ex", n, ctypes.c_void_p(pptr), ctypes.c_void_p(gptr), self._GDTYPE,
                        ctypes.c_void_p(hs.m.data_ptr() + hoff * esz), ctypes.c_void_p(hs.v.data_ptr() + hoff * esz),

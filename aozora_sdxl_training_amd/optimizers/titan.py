@@ -29,9 +29,10 @@ class TitanAdamW(RavenAdamW):
     _GSIZE = 4
 
     def __init__(self, params, lr: float = 1e-4, betas=(0.9, 0.999), weight_decay: float = 0.01, eps: float = 1e-8,
-                 debias_strength: float = 1.0, momentum_dtype: torch.dtype = torch.bfloat16):
+                 debias_strength: float = 1.0, momentum_dtype: torch.dtype = torch.bfloat16, stochastic_rounding: bool = False,
+                 sr_seed: int = 0):
         super().__init__(params, lr=lr, betas=betas, weight_decay=weight_decay, eps=eps, debias_strength=debias_strength,
-                         momentum_dtype=momentum_dtype)
+                         momentum_dtype=momentum_dtype, stochastic_rounding=stochastic_rounding, sr_seed=sr_seed)
         self._cpu_grads: Dict[torch.Tensor, torch.Tensor] = {}
         self._cpu_grad_ready = set()
         self._hook_handles = []

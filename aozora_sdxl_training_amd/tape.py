@@ -36,7 +36,7 @@ _KERNEL_ENTRIES = frozenset({
     "az_ln_param_finish_multi", "az_geglu_fwd", "az_geglu_bwd", "az_silu_fwd", "az_silu_bwd", "az_add_rows", "az_upsample2x_fwd",
     "az_upsample2x_bwd", "az_upsample_nearest_fwd", "az_upsample_nearest_bwd", "az_colsum", "az_colsum_grad", "az_reduce_segs_to_bf16", "az_transpose_bf16", "az_transpose_bf16_batched",
     "az_transpose_multi_bf16", "az_f32_to_bf16", "az_timestep_embed", "az_nchw_to_nhwc_pad", "az_nhwc_to_nchw", "az_noise_target",
-    "az_mse_loss_fwd_bwd", "az_sumsq_bf16", "az_sumsq", "az_clip_coef", "az_adamw_flat", "az_adamw_flat_ex", "az_scale_bf16",
+    "az_mse_loss_fwd_bwd", "az_sumsq_bf16", "az_sumsq", "az_clip_coef", "az_adamw_flat", "az_adamw_flat_ex", "az_adamw_flat_sr", "az_scale_bf16",
     "az_scale_f32", "az_stage_inputs", "az_adamw8bit_step"})
 # ... and the ones with a stream argument that end in something else (graph capture / launch, event and stream calls, copies)
 _NOT_KERNEL_ENTRIES = frozenset({"az_graph_begin", "az_graph_end", "az_graph_launch", "az_event_record", "az_stream_wait_event",

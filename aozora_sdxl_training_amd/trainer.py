@@ -29,6 +29,8 @@ from .train_step import TrainStep
 
 _RAVEN_DEFAULTS = dict(betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, debias_strength=0.3, momentum_dtype="bfloat16")
 _ADAMW8_DEFAULTS = dict(betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)      # config.py PAGED_ADAMW_8BIT_PARAMS
+_SR_8BIT_REFUSAL = ("stochastic_rounding is an option of raven and titan (RAVEN_PARAMS / TITAN_PARAMS): paged_adamw_8bit writes its "
+                    "parameters through two roundings of its own, a different contract -- remove the key from PAGED_ADAMW_8BIT_PARAMS")
 _ADAMW8_DP_REFUSAL = "paged_adamw_8bit runs at one rank only: data-parallel training supports raven and titan"
 
 
@@ -61,7 +63,15 @@ def _optimizer(config, params):
     mdt = _momentum_dtype(hp.pop("momentum_dtype", "bfloat16"))
     cls = TitanAdamW if kind == "titan" else RavenAdamW
     return cls([{"params": params, "lr_scale": 1.0}], lr=lr, betas=tuple(hp["betas"]), eps=hp["eps"], weight_decay=hp["weight_decay"],
-               debias_strength=hp["debias_strength"], momentum_dtype=mdt)
+               debias_strength=hp["debias_strength"], momentum_dtype=mdt, **_sr_args(config, hp))
+
+
+def _sr_args(config, hp):
+    """"stochastic_rounding": true in RAVEN_PARAMS / TITAN_PARAMS (absent = false; not in the reference) -> the optimizers' keywords;
+    the seed is the run's SEED, so a resumed run (same seed, restored step count) draws the bits the uninterrupted run draws."""
+    on = hp.get("stochastic_rounding", False)
+    on = on.strip().lower() in ("true", "1", "t", "y", "yes") if isinstance(on, str) else bool(on)      # config.coerce_types' reading of a bool
+    return dict(stochastic_rounding=on, sr_seed=int(getattr(config, "SEED", 0) or 0))
 
 
 def _optimizer_8bit(config, params):
@@ -69,6 +79,8 @@ def _optimizer_8bit(config, params):
     curve = getattr(config, "LR_CUSTOM_CURVE", [])
     lr = max(p[1] for p in curve) if curve else config.LEARNING_RATE
     hp = {**_ADAMW8_DEFAULTS, **dict(getattr(config, "PAGED_ADAMW_8BIT_PARAMS", {}) or {})}
+    if "stochastic_rounding" in hp:
+        raise ValueError(_SR_8BIT_REFUSAL)
     return PagedAdamW8bit(params, lr=lr, betas=tuple(hp["betas"]), eps=hp["eps"], weight_decay=hp["weight_decay"], min_8bit_size=4096)
 
 
@@ -135,9 +147,12 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
             force_local=not dp,
             # m / v stay resident in HBM (10.3 GB of 288) unless the preset asks for the reference's residency -- pinned host memory,
             # streamed over the host link every optimizer step (raven.py:83-84, 114-117) -- with RAVEN_STATE_ON_HOST = true
-            state_on_host=bool(getattr(config, "RAVEN_STATE_ON_HOST", False)))
+            state_on_host=bool(getattr(config, "RAVEN_STATE_ON_HOST", False)), **_sr_args(config, hp))
     else:
         optimizer = _optimizer(config, params)
+    if rank == 0 and getattr(optimizer, "sr", getattr(optimizer, "_sr", False)):
+        print(f"INFO: stochastic rounding of the bf16 parameter update is ON (seed {int(getattr(config, 'SEED', 0) or 0)}): an option outside "
+              "the reference; results differ from the default round-to-nearest write-back")
     flat_opt = isinstance(optimizer, ShardedRaven)
     lr_scheduler = CustomCurveLRScheduler(optimizer, config.LR_CUSTOM_CURVE, config.MAX_TRAIN_STEPS)
     if getattr(config, "RESUME_TRAINING", False):

@@ -364,6 +364,25 @@ int az_adamw_flat_ex(long n, void* p, const void* g, int gdtype, void* m, void* 
 int az_raven_step_ex(long n, void* p, const void* g, int gdtype, void* m_host, void* v_host, int mdtype, const void* hyper,
                      const void* coef, void* staging, long chunk_elems, void* stream_compute, void* stream_h2d,
                      void* stream_d2h);
+/* _sr variants (an option the reference does not have; off by default -- INTEGRATION.md "Stochastic rounding"): the same arithmetic and
+ * the same m / v as the _ex entry points, but the fp32 result is written to the bf16 parameter with STOCHASTIC rounding instead of
+ * round-to-nearest-even: o = (bits(pp) + r) >> 16 with r uniform in [0, 65536) (non-finite pp, and a carry into the all-ones exponent,
+ * excepted), so the magnitude rounds up with probability (low half) / 65536 and a representable value never changes.  r comes from
+ * Philox4x32-10: key = (seed low word, seed high word), counter = (group low word, group high word, step, domain) with
+ * group = e >> 3 for the element's GLOBAL index e = elem0 + offset in the call; element e takes the low (e even) or high (e odd)
+ * half of output word (e & 7) >> 1.  The bits of an element therefore do not depend on how a flat range is cut into calls, chunks,
+ * regions or rank shards; the caller keeps (seed, step, domain, e) distinct for all elements updated in one step.  16-byte accesses
+ * when (elem0 + i) % 8 == 0 coincides with 16-byte alignment of p, g, m, v, element-wise otherwise.  elem0 >= 0.
+ * `step` is an argument, not device memory: the optimizer step is issued eagerly.  Should it ever be issued from a recorded tape,
+ * step (and the hyper vector's contents) must not be frozen into the recording. */
+/* ref: raven.py:144 (p.copy_(p32): the bf16 write-back being varied), raven.py:89-149, titan.py:230-296 */
+int az_adamw_flat_sr(long n, void* p, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper,
+                     const void* coef, long seed, long step, long domain, long elem0, void* stream);
+/* the chunked pinned-host pipeline of az_raven_step_ex; chunk c is launched with elem0 + c * chunk_elems */
+/* ref: raven.py:103-149, raven.py:144, titan.py:230-296 */
+int az_raven_step_sr(long n, void* p, const void* g, int gdtype, void* m_host, void* v_host, int mdtype, const void* hyper,
+                     const void* coef, void* staging, long chunk_elems, void* stream_compute, void* stream_h2d,
+                     void* stream_d2h, long seed, long step, long domain, long elem0);
 /* g_bf16[i] = bf16(g[i] * coef[0]) in place -- the in-place clip of torch.nn.utils.clip_grad_norm_
  * (train.py:2775-2778); skipped entirely when coef[0] == 1 */
 /* ref: train.py:2775-2778 (in-place gradient scaling of clip_grad_norm_) */
