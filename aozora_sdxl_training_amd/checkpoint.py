@@ -149,8 +149,9 @@ def save_model(output_path, unet_or_state, base_checkpoint_path, compute_dtype=t
     return merged, missing
 
 
-def save_training_state(path, global_step, micro_step, optimizer, sampler_seed, sampler_epoch, timestep_sampler=None):
-    """train.py:2513-2531 (same dict keys, so either trainer can resume the other's file)."""
+def save_training_state(path, global_step, micro_step, optimizer, sampler_seed, sampler_epoch, timestep_sampler=None, extra=None):
+    """train.py:2513-2531 (same dict keys, so either trainer can resume the other's file).  `extra`: further keys of options the
+    reference does not have ("ema_state"); its loader reads keys by name and never sees them."""
     optim_state = optimizer.save_cpu_state() if hasattr(optimizer, "save_cpu_state") else optimizer.state_dict()
     st = {
         "global_step": global_step, "micro_step": micro_step, "optimizer_state": optim_state,
@@ -160,6 +161,8 @@ def save_training_state(path, global_step, micro_step, optimizer, sampler_seed, 
         "torch_cpu_state": torch.get_rng_state(),
         "torch_cuda_state": torch.cuda.get_rng_state() if torch.cuda.is_available() else None,
     }
+    if extra:
+        st.update(extra)
     Path(path).parent.mkdir(parents=True, exist_ok=True)
     torch.save(st, str(path))
     return st
@@ -235,6 +238,11 @@ def output_model_stem(config, source_path) -> str:
     stem = want if want else f"{src}_trained_{tag}"
     config._RESOLVED_OUTPUT_STEM = stem
     return stem
+
+
+def ema_names(output_stem: str, global_step: Optional[int] = None) -> str:
+    """File of the EMA weights ("ema_decay", not in the reference): next to a checkpoint's model file, or -- no step -- the final one."""
+    return f"{output_stem}_ema.safetensors" if global_step is None else f"{output_stem}_step_{global_step}_ema.safetensors"
 
 
 def checkpoint_names(output_stem: str, global_step: int):

@@ -320,6 +320,35 @@ int launch_adamw_sr(long n, void* p, const void* g, int gdtype, void* m, void* v
   return AZ_OK;
 }
 
+// ---- fp32 exponential moving average of the bf16 parameters (an option the reference does not have: INTEGRATION.md) -------------------
+// diffusers' EMAModel.step form, s.sub_(one_minus_decay * (s - p)): three fp32 operations, three roundings, no contraction.
+__device__ __forceinline__ float ema_math(float e, float p, float omd) {
+#pragma clang fp contract(off)
+  float t = e - p;
+  t = omd * t;
+  return e - t;
+}
+
+// az_ema_flat: the scalar head [0, head), then `groups` groups of 8 elements with 16-byte accesses (one load of p, two loads and two
+// stores of e per thread), then the scalar tail up to n -- the split of adamw_sr_kernel (launch_ema computes it).
+__global__ void ema_kernel(long n, const bf16_t* __restrict__ p, float* __restrict__ e, float omd, long head, long groups) {
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long)gridDim.x * blockDim.x;
+  const long body = head + (groups << 3);                    // <= n (launch_ema)
+  for (long gi = tid; gi < groups; gi += nthr) {
+    const long i = head + (gi << 3);
+    float pp[8], ee[8];
+    load8<bf16_t>(p + i, pp); load8<float>(e + i, ee);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) ee[k] = ema_math(ee[k], pp[k], omd);
+    store8_moment<float>(e + i, ee);
+  }
+  const long nscalar = n - (groups << 3);                    // head + tail
+  for (long j = tid; j < nscalar; j += nthr) {
+    const long i = j < head ? j : j - head + body;
+    e[i] = ema_math(e[i], bf2f(p[i]), omd);
+  }
+}
+
 // Hand-off events of the chunk pipeline, one set per COMPUTE STREAM (a stream belongs to one device, so two optimizers,
 // threads or devices in one process never share a set); creation is serialised by a mutex.  Calls that name the same
 // compute stream must come from one host thread at a time -- the stream's own order is what sequences them.
@@ -439,6 +468,21 @@ int az_adamw_flat_sr(long n, void* p, const void* g, int gdtype, void* m, void* 
                      long seed, long step, long domain, long elem0, void* stream) {
   if (n <= 0) return AZ_ERR_ARG(63);
   return launch_adamw_sr(n, p, g, gdtype, m, v, mdtype, hyper, coef, seed, step, domain, elem0, (hipStream_t)stream);
+}
+
+int az_ema_flat(long n, const void* p, void* ema_f32, float one_minus_decay, void* stream) {
+  if (n < 0 || !p || !ema_f32 || ((uintptr_t)p & 1) || ((uintptr_t)ema_f32 & 3)) return AZ_ERR_ARG(69);
+  if (n == 0) return AZ_OK;
+  // first element where p AND e are 16-byte aligned: p + 2 h and e + 4 h, h in [0, 8); none (the two pointers cannot be co-aligned) or
+  // beyond the range: every element takes the scalar form
+  long head = n;
+  for (long h = 0; h < 8; ++h)
+    if ((((uintptr_t)p + 2 * h) & 15) == 0 && (((uintptr_t)ema_f32 + 4 * h) & 15) == 0) { head = h < n ? h : n; break; }
+  const long groups = (n - head) >> 3, nscalar = n - (groups << 3);
+  az_launch(ema_kernel, dim3(grid_for(groups > nscalar ? groups : nscalar)), dim3(256), 0, (hipStream_t)stream, n, (const bf16_t*)p,
+            (float*)ema_f32, one_minus_decay, head, groups);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
 }
 
 int az_raven_step_ex(long n, void* p, const void* g, int gdtype, void* m_host, void* v_host, int mdtype, const void* hyper,

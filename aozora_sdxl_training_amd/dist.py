@@ -99,13 +99,27 @@ def all_gather_flat(dist, flat: torch.Tensor, rank: int, world: int, group=None)
             flat[a:b].copy_(part)
 
 
+def all_reduce_flat(dist, flat: torch.Tensor, group=None):
+    """In place: the SUM over ranks of a flat buffer (checkpoint-time gathers: ema.EmaWeights.full)."""
+    gloo = dist.get_backend(group) != "nccl"
+    if gloo:
+        _gloo_fence(flat)
+    dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+    if gloo:
+        _gloo_fence(flat)
+
+
 class ShardedRaven:
-    """Raven (raven.py:89-149 arithmetic) over the flat buffers of an AozoraUNet, sharded across ranks."""
+    """Raven (raven.py:89-149 arithmetic) over the flat buffers of an AozoraUNet, sharded across ranks.
+
+    ema (not in the reference, None = off): an ema.EmaWeights that tracks exactly this optimizer's owned trainable elements, or
+    dict(decay=, warmup=) from which that shard is built here, in the layout of m_dev / v_dev (the owned ranges exist only now); either
+    way it is `self.ema`, and step() issues its launches on the streams that update each range."""
 
     def __init__(self, unet, lr=8e-7, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, debias_strength=0.3,
                  momentum_dtype=torch.bfloat16, clip_grad_norm=1.0, process_group=None, force_local=False,
                  overlap=True, regions: Optional[int] = None, force_exchange=False, state_on_host=False,
-                 stochastic_rounding: bool = False, sr_seed: int = 0):
+                 stochastic_rounding: bool = False, sr_seed: int = 0, ema=None):
         import torch.distributed as dist
         self.unet = unet
         # stochastic rounding of the bf16 write-back (not in the reference, off by default: optimizers.RavenAdamW): the random bits are
@@ -188,6 +202,31 @@ class ShardedRaven:
                 stream_check(self.comm, other, f"exchange stream / {name}", if_bad="share a hardware queue (measured harmless for the exchange stream)")
         self._ev = None
         self._timing = None
+        # fp32 EMA of the owned trainable elements (ema.EmaWeights; not in the reference, None = off: no launch, allocation or event
+        # differs).  Given as an EmaWeights, or as dict(decay=, warmup=) from which the shard is built in the layout of m_dev / v_dev.
+        self.ema = self._make_ema(ema, force_local)
+
+    def _make_ema(self, ema, force_local):
+        if ema is None:
+            return None
+        from .ema import EmaWeights
+        if isinstance(ema, dict):
+            return EmaWeights(self.unet, ema["decay"], ema.get("warmup", True), ranges=[r for rs in self.ranges for r in rs],
+                              offsets=[o for os_ in self.range_off for o in os_], process_group=self.pg, force_local=force_local)
+        if ema.unet is not self.unet or ema.numel != self.shard or (ema.world, ema.rank) != (self.world, self.rank):
+            raise ValueError("the EMA does not track this optimizer's owned trainable elements (another UNet, freeze mask, world size or rank)")
+        for rs in self.ranges:
+            for a, b in rs:
+                ema.offset_of(a, b)            # ValueError: an owned range the EMA does not track
+        return ema
+
+    def _ema_regions(self, regions, stream):
+        """EMA launches of the owned ranges of `regions` on `stream` (the stream that updated them); no EMA: nothing."""
+        if self.ema is None:
+            return
+        for i in regions:
+            for a, b in self.ranges[i]:
+                self.ema.update_range(a, b, stream)
 
     # ---- optional event timing of the exchange (bench.py: exposed boundary, per-region collective rates, m/v copies) --------
     def enable_timing(self, on=True):
@@ -294,6 +333,8 @@ class ShardedRaven:
         boundary.__enter__()
         self._boundary = boundary
         self.step_count += 1
+        if self.ema is not None:
+            self.ema.begin_update()
         # a step without a forward in between (tests): the previous step's gathers AND its region-1 / 2 updates (side / comm
         # stream, they read hyper_dev and scal[1]) must have finished before the hyper-parameters and the clip scalars are rewritten
         u.wait_tail_params()
@@ -347,6 +388,10 @@ class ShardedRaven:
             # the compute streams and the window's last micro-steps ran 124 / 161 ms instead of 117 -- measured, streams.py)
             bg = self._bg = u._sides[0]
             update_region(0, main)                     # what the forward reads first stays on the main stream (3 % of the elements)
+            # region 0's EMA goes IN FRONT of the hand-over: the background updates then start 0.13 ms later (SDXL-base), which the forward
+            # never sees -- behind the hand-over it shares the device with region 1's update and held the main stream 0.88 ms instead
+            # (tools/ema_time.py, INTEGRATION.md "EMA of the weights")
+            self._ema_regions((0,), main)
             bg.wait_stream(main)                       # clip coefficient, hyper-parameters, m / v staging are all ordered before this point
             with torch.cuda.stream(bg):
                 later = []
@@ -360,6 +405,7 @@ class ShardedRaven:
                     for lo, hi in self.regions:        # W^T copies: read by the next BACKWARD only, so they queue behind the updates
                         u._refresh_jobs(lo, hi)
                 u._wt_ready = torch.cuda.Event(); u._wt_ready.record(bg)
+                self._ema_regions((1, 2), bg)          # behind the region events: the forward never waits for these
             for i, ev in later:
                 u.set_region_params_event(i, ev)
             u.transposed_refreshed_externally()
@@ -375,6 +421,7 @@ class ShardedRaven:
             update_region(0, main)
             upd0 = torch.cuda.Event(); upd0.record(main)       # (also orders the clip coefficient, the hyper-parameters and the m / v staging)
             self.comm.wait_event(upd0)
+            self._ema_regions((0,), main)              # reads this rank's own shard only: runs beside all-gather(0), which does not write it
             with torch.cuda.stream(self.comm):
                 self._gather_region(0)
                 u._refresh_jobs(*self.regions[0])
@@ -388,6 +435,7 @@ class ShardedRaven:
                     u._refresh_jobs(*self.regions[i])
                     ev = torch.cuda.Event(); ev.record(self.comm)
                     later.append((i, ev))
+                self._ema_regions((1, 2), self.comm)   # behind the gathers and their events, ahead of the next step's updates on this stream
             main.wait_event(head)
             for i, ev in later:
                 u.set_region_params_event(i, ev)
@@ -439,13 +487,15 @@ class ShardedRaven:
                         u._refresh_jobs(*self.regions[i])
                         ev = torch.cuda.Event(); ev.record(self.comm)
                         later.append((i, ev))
+                self._ema_regions(range(len(self.ranges)), main)      # beside the gathers (they read, and leave alone, the owned shards)
                 main.wait_event(head)
                 for i, ev in later:
                     u.set_region_params_event(i, ev)
                 u.transposed_refreshed_externally()
-            else:
-                for i in range(len(self.regions)):
-                    self._gather_region(i)
+                return
+            for i in range(len(self.regions)):
+                self._gather_region(i)
+        self._ema_regions(range(len(self.ranges)), main)              # behind the update and whatever the next forward waits for
 
     def zero_grad(self, set_to_none=True):
         if self._update_inflight:
@@ -582,6 +632,8 @@ class ShardedRaven:
             return
         if self._d2h_done is not None:
             self._d2h_done.synchronize()
+        if self.ema is not None:
+            self.ema.synchronize()
 
 
 class ShardedTitan(ShardedRaven):
@@ -664,6 +716,8 @@ class ShardedTitan(ShardedRaven):
         if not self._acc_started:
             raise RuntimeError("ShardedTitan.step() without accumulate(): no gradients in the fp32 accumulator")
         self.step_count += 1
+        if self.ema is not None:
+            self.ema.begin_update()
         self._hyper()
         self.prefetch()
         u.wait_tail_params()

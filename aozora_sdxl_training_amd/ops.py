@@ -672,3 +672,14 @@ def sumsq(g, out_f32, accumulate):
 
 def clip_coef(sumsq_f32, max_norm, coef, norm, unscale=1.0):
     lib().call("az_clip_coef", _ptr(sumsq_f32), float(max_norm), float(unscale), _ptr(coef), _ptr(norm), _stream())
+
+
+def ema_flat(p, ema, one_minus_decay, stream=None):
+    """ema <- ema - omd * (ema - float(p)) in place: p bf16 (read only), ema fp32, both 1-D and contiguous, on `stream` (default: the
+    current one).  An empty range launches nothing."""
+    _req(p.is_cuda and ema.is_cuda and p.device == ema.device and p.dtype == BF16 and ema.dtype == F32, "ema_flat needs cuda bf16 p and fp32 ema")
+    _req(p.dim() == 1 and ema.dim() == 1 and p.numel() == ema.numel() and p.is_contiguous() and ema.is_contiguous(), "ema_flat shapes")
+    if p.numel() == 0:             # (an empty tensor has no address to hand over)
+        return
+    st = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    lib().call("az_ema_flat", p.numel(), _ptr(p), _ptr(ema), float(one_minus_decay), st)

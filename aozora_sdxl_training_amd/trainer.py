@@ -21,6 +21,7 @@ import torch
 from . import checkpoint as ckpt
 from . import data as feed
 from .clip import clip_grad_norm_
+from .ema import EmaWeights, read_options as _ema_options
 from .optimizers import PagedAdamW8bit, RavenAdamW, TitanAdamW
 from .schedule import (CustomCurveLRScheduler, TimestepSampler, ddpm_alphas_cumprod, generate_noise, make_time_ids,
                        seeded_torch_generator, timestep_loss_curve_from_config, trainable_mask)
@@ -94,20 +95,26 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     import torch.distributed as tdist
     dp = tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1
     world, rank = (tdist.get_world_size(), tdist.get_rank()) if dp else (1, 0)
-    eightbit = str(getattr(config, "OPTIMIZER_TYPE", "raven")).lower() == "paged_adamw_8bit"
+    kind = str(getattr(config, "OPTIMIZER_TYPE", "raven")).lower()
+    eightbit = kind == "paged_adamw_8bit"
     if eightbit and dp:
         raise ValueError(_ADAMW8_DP_REFUSAL)
+    # "ema_decay" [, "ema_warmup"] in the ACTIVE optimizer's dictionary: an fp32 EMA of the trainable weights (ema.py; not in the
+    # reference, absent = off).  Read first: an invalid value is refused before anything is allocated.
+    ema_decay, ema_warmup = _ema_options(getattr(config, {"titan": "TITAN_PARAMS", "paged_adamw_8bit": "PAGED_ADAMW_8BIT_PARAMS"}.get(kind, "RAVEN_PARAMS"), None))
     GA = int(config.GRADIENT_ACCUMULATION_STEPS)
     mode = getattr(config, "PREDICTION_TYPE", "epsilon")
     config.is_rectified_flow = (mode == "rectified_flow")
     micro_step = optimizer_step = 0
     model_to_load = Path(config.SINGLE_FILE_CHECKPOINT_PATH)
     sampler_seed, optimizer_state, ts_state = config.SEED, None, None
+    ema_saved = None
     if getattr(config, "RESUME_TRAINING", False):                                   # train.py:2558-2573
         rs = ckpt.load_training_state(config.RESUME_STATE_PATH, GA)
         micro_step, optimizer_step = rs["micro_step"], rs["optimizer_step"]
         sampler_seed, ts_state, optimizer_state = rs["sampler_seed"], rs["timestep_sampler_state"], rs["optimizer_state"]
         model_to_load = Path(config.RESUME_MODEL_PATH)
+        ema_saved = rs["raw"].get("ema_state")
         ckpt.restore_rng(rs["raw"])
     if unet is None:
         unet = ckpt.load_unet(model_to_load, device)
@@ -123,7 +130,7 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     loss_curve = timestep_loss_curve_from_config(config, 1000)
     step = TrainStep(unet, mode=mode, grad_accum=GA, world_size=world, loss_curve=loss_curve, use_graph=False)
     from .dist import ShardedRaven, ShardedTitan
-    titan = str(getattr(config, "OPTIMIZER_TYPE", "raven")).lower() == "titan"
+    titan = kind == "titan"
     # Single-GPU Titan: the device-accumulator form (dist.ShardedTitan in a group of one: fp32 gradient accumulator in HBM, the same
     # arithmetic -- titan.py:119-131, 162-184, 230-296 -- tests/test_fullsize_gpu.py cfg5) unless the preset asks for the reference's
     # residency with TITAN_HOST_GRADIENTS = true (optimizers.TitanAdamW: fp32 gradients in pinned HOST memory, 10.3 GB written over the
@@ -147,20 +154,34 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
             force_local=not dp,
             # m / v stay resident in HBM (10.3 GB of 288) unless the preset asks for the reference's residency -- pinned host memory,
             # streamed over the host link every optimizer step (raven.py:83-84, 114-117) -- with RAVEN_STATE_ON_HOST = true
-            state_on_host=bool(getattr(config, "RAVEN_STATE_ON_HOST", False)), **_sr_args(config, hp))
+            state_on_host=bool(getattr(config, "RAVEN_STATE_ON_HOST", False)), **_sr_args(config, hp),
+            ema=dict(decay=ema_decay, warmup=ema_warmup) if ema_decay is not None else None)
     else:
         optimizer = _optimizer(config, params)
     if rank == 0 and getattr(optimizer, "sr", getattr(optimizer, "_sr", False)):
         print(f"INFO: stochastic rounding of the bf16 parameter update is ON (seed {int(getattr(config, 'SEED', 0) or 0)}): an option outside "
               "the reference; results differ from the default round-to-nearest write-back")
     flat_opt = isinstance(optimizer, ShardedRaven)
+    # the flat optimizers issue the EMA launches themselves, on the streams that update each range; a module optimizer's step() is
+    # followed by ema.update() in the loop
+    ema = None if ema_decay is None else (optimizer.ema if flat_opt else EmaWeights(unet, ema_decay, ema_warmup))
+    if rank == 0 and ema is not None:
+        print(f"INFO: EMA of the trainable weights is ON (decay {ema_decay}, warm-up {'on' if ema_warmup else 'off'}, {ema.nbytes} bytes of fp32 on this "
+              "rank): an option outside the reference")
     lr_scheduler = CustomCurveLRScheduler(optimizer, config.LR_CUSTOM_CURVE, config.MAX_TRAIN_STEPS)
     if getattr(config, "RESUME_TRAINING", False):
         if dp:       # every rank resumes its own shard (written next to rank 0's training-state file)
             shard = torch.load(str(config.RESUME_STATE_PATH) + f".rank{rank}", map_location="cpu", weights_only=False)
+            ema_saved = shard.get("ema_state")
             ckpt.resume_optimizer(optimizer, shard, lr_scheduler, micro_step)
         else:
             ckpt.resume_optimizer(optimizer, optimizer_state, lr_scheduler, micro_step)
+        if ema is not None and ema_saved is not None:
+            ema.load_state(ema_saved)
+        elif ema is not None and rank == 0:
+            print("INFO: the training state holds no EMA (\"ema_state\"): the EMA starts from the loaded parameters with k = 0")
+        elif ema_saved is not None and rank == 0:
+            print("INFO: the training state holds an EMA (\"ema_state\") but \"ema_decay\" is not set: ignored")
 
     dataset = feed.CachedLatentDataset(config)
     timestep_sampler = TimestepSampler(config)
@@ -184,6 +205,8 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     noise_gen = torch.Generator()
     clip = float(config.CLIP_GRAD_NORM)
     hist = dict(losses=[], grad_norms=[], lrs=[], saved=[])
+    if ema is not None:
+        hist["saved_ema"] = []
     # emergency-save flag: the GUI writes PROJECT_ROOT/force_save.flag and runs the trainer with cwd = PROJECT_ROOT
     # (gui.py:5947, 5983; train.py:2550 looks next to itself) -> default = the process' working directory
     flag = Path(getattr(config, "FORCE_SAVE_FLAG", None) or Path.cwd() / "force_save.flag")
@@ -338,6 +361,8 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
                         unet.expose_grads()
                         raw = float(clip_grad_norm_(unet, clip if clip > 0 else float("inf")).item())
                         optimizer.step()
+                    if ema is not None and not flat_opt:
+                        ema.update()                              # same stream, right behind the step
                     optimizer.zero_grad(set_to_none=True)
                     optimizer_step += 1
                     if not gc_frozen:           # the launch tapes / pools built during the first window are permanent: keep the cyclic
@@ -365,16 +390,25 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
                         mname, sname = ckpt.checkpoint_names(stem, optimizer_step)
                         if hasattr(optimizer, "synchronize_params"):
                             optimizer.synchronize_params()      # updates / all-gathers still running under the next forward's slots must have landed
+                        # EMA: every rank takes part in the gather (state_dict) and keeps its own fp32 shard; rank 0 writes the file
+                        ema_sd = ema.state_dict() if ema is not None else None
+                        ema_extra = {"ema_state": ema.save_state()} if ema is not None else None
                         if dp:
                             Path(config.OUTPUT_DIR).mkdir(parents=True, exist_ok=True)
-                            torch.save(optimizer.save_cpu_state(), str(Path(config.OUTPUT_DIR) / sname) + f".rank{rank}")
+                            torch.save({**optimizer.save_cpu_state(), **(ema_extra or {})}, str(Path(config.OUTPUT_DIR) / sname) + f".rank{rank}")
                         if rank == 0:
                             ckpt.save_model(Path(config.OUTPUT_DIR) / mname, unet, model_to_load, torch.bfloat16)
+                            if ema is not None:
+                                ckpt.save_model(Path(config.OUTPUT_DIR) / ckpt.ema_names(stem, optimizer_step), ema_sd, model_to_load, torch.bfloat16)
                             ckpt.save_training_state(Path(config.OUTPUT_DIR) / sname, optimizer_step, micro_step,
-                                                     _NoState() if dp else optimizer, sampler.seed, sampler.epoch, timestep_sampler)
+                                                     _NoState() if dp else optimizer, sampler.seed, sampler.epoch, timestep_sampler,
+                                                     extra=None if dp else ema_extra)
+                        del ema_sd
                         if dp:
                             tdist.barrier()
                         hist["saved"].append((mname, sname))
+                        if ema is not None:
+                            hist["saved_ema"].append(ckpt.ema_names(stem, optimizer_step))
                     if not flat_opt:
                         flush()                                  # the module-optimizer paths read their norm on the host: nothing left to wait for
             if n_batches == 0:
@@ -394,12 +428,17 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     final = Path(config.OUTPUT_DIR) / f"{stem}.safetensors"
     if hasattr(optimizer, "synchronize_params"):
         optimizer.synchronize_params()           # the last step's overlapped update / all-gather must have landed
+    ema_sd = ema.state_dict() if ema is not None else None       # (every rank: the gather is a collective)
     if rank == 0:
         ckpt.save_model(final, unet, model_to_load, torch.bfloat16)
+        if ema is not None:
+            ckpt.save_model(Path(config.OUTPUT_DIR) / ckpt.ema_names(stem), ema_sd, model_to_load, torch.bfloat16)
         print("All tasks complete. Final model saved.")
     if dp:
         tdist.barrier()
     hist.update(micro_step=micro_step, optimizer_step=optimizer_step, final_model=str(final))
+    if ema is not None:
+        hist["final_ema_model"] = str(Path(config.OUTPUT_DIR) / ckpt.ema_names(stem))
     return hist
 
 

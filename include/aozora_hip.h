@@ -383,6 +383,14 @@ int az_adamw_flat_sr(long n, void* p, const void* g, int gdtype, void* m, void* 
 int az_raven_step_sr(long n, void* p, const void* g, int gdtype, void* m_host, void* v_host, int mdtype, const void* hyper,
                      const void* coef, void* staging, long chunk_elems, void* stream_compute, void* stream_h2d,
                      void* stream_d2h, long seed, long step, long domain, long elem0);
+/* fp32 exponential moving average of bf16 parameters over a flat range (an option the reference does not have; off by default --
+ * INTEGRATION.md "EMA of the weights"): e[i] <- e[i] - omd * (e[i] - float(p[i])), i in [0, n), omd = 1 - decay.  p bf16 (read only),
+ * e fp32 (in place).  Three fp32 operations, each rounded (no contraction): t = e - float(p); t = omd * t; e = e - t -- the form of
+ * diffusers' EMAModel.step.  NaN and inf follow IEEE rules; omd == 1 is not special.  16-byte accesses from the first element at which p
+ * and e are both 16-byte aligned, element-wise before it, in the tail, and everywhere when the two cannot be co-aligned.  n == 0
+ * returns 0 without a launch; n < 0, a null pointer, p not 2-byte aligned or e not 4-byte aligned are argument errors. */
+/* ref: not in the reference; runs behind `optimizer.step()`, train.py:2783 */
+int az_ema_flat(long n, const void* p, void* ema_f32, float one_minus_decay, void* stream);
 /* g_bf16[i] = bf16(g[i] * coef[0]) in place -- the in-place clip of torch.nn.utils.clip_grad_norm_
  * (train.py:2775-2778); skipped entirely when coef[0] == 1 */
 /* ref: train.py:2775-2778 (in-place gradient scaling of clip_grad_norm_) */
