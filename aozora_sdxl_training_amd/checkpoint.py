@@ -151,7 +151,7 @@ def save_model(output_path, unet_or_state, base_checkpoint_path, compute_dtype=t
 
 def save_training_state(path, global_step, micro_step, optimizer, sampler_seed, sampler_epoch, timestep_sampler=None, extra=None):
     """train.py:2513-2531 (same dict keys, so either trainer can resume the other's file).  `extra`: further keys of options the
-    reference does not have ("ema_state"); its loader reads keys by name and never sees them."""
+    reference does not have ("ema_state", "master_state"); its loader reads keys by name and never sees them."""
     optim_state = optimizer.save_cpu_state() if hasattr(optimizer, "save_cpu_state") else optimizer.state_dict()
     st = {
         "global_step": global_step, "micro_step": micro_step, "optimizer_state": optim_state,

@@ -349,6 +349,70 @@ __global__ void ema_kernel(long n, const bf16_t* __restrict__ p, float* __restri
   }
 }
 
+// ---- fp32 master weights (an option the reference does not have: INTEGRATION.md "fp32 master weights") -------------------------------
+// az_adamw_flat_master: adamw_math with the fp32 master w[i] as the parameter operand; writes w[i] = pp and p[i] = bf16(pp), round to
+// nearest even -- p is never read.  The split of adamw_sr_kernel / ema_kernel: scalar head [0, head), `groups` groups of 8 elements
+// with 16-byte accesses (two loads and two stores of w per thread), scalar tail (launch_adamw_master computes it).
+template <typename TM, typename TG>
+__global__ void adamw_master_kernel(long n, bf16_t* __restrict__ p, float* __restrict__ w, const TG* __restrict__ g, TM* __restrict__ m,
+                                    TM* __restrict__ v, const float* __restrict__ hyper, const float* __restrict__ coef, long head, long groups) {
+  const AdamwK k = adamw_consts(hyper, coef);
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long)gridDim.x * blockDim.x;
+  const long body = head + (groups << 3);                    // <= n (launch_adamw_master)
+  for (long gi = tid; gi < groups; gi += nthr) {
+    const long i = head + (gi << 3);
+    float gg[8], mm[8], vv[8], pp[8];
+    load8<TG>(g + i, gg); load8<TM>(m + i, mm); load8<TM>(v + i, vv); load8<float>(w + i, pp);
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      adamw_math<TG>(k, [&] { return gg[e]; }, [&] { return mm[e]; }, [&] { return vv[e]; }, [&] { return pp[e]; }, mm[e], vv[e], pp[e]);
+    store8_moment<float>(w + i, pp);
+    store8_moment<bf16_t>(p + i, pp);
+    store8_moment<TM>(m + i, mm);
+    store8_moment<TM>(v + i, vv);
+  }
+  const long nscalar = n - (groups << 3);                    // head + tail
+  for (long j = tid; j < nscalar; j += nthr) {
+    const long i = j < head ? j : j - head + body;
+    float mm, vv, pp;
+    adamw_math<TG>(k, [&] { return ldf<TG>(g, i); }, [&] { return ldf<TM>(m, i); }, [&] { return ldf<TM>(v, i); }, [&] { return w[i]; },
+                   mm, vv, pp);
+    w[i] = pp;
+    p[i] = f2bf(pp);
+    stf<TM>(m, i, mm);
+    stf<TM>(v, i, vv);
+  }
+}
+
+int launch_adamw_master(long n, void* p, void* w, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper,
+                        const void* coef, hipStream_t st) {
+  const size_t esz = mdtype == 1 ? 4 : 2, gsz = gdtype == 0 ? 2 : 4;
+  // first element where p, g, m, v AND w are 16-byte aligned, h in [0, 8); none (the five pointers cannot be co-aligned) or beyond
+  // the range: every element takes the scalar form
+  long head = n;
+  for (long h = 0; h < 8; ++h)
+    if ((((uintptr_t)p + 2 * h) & 15) == 0 && (((uintptr_t)w + 4 * h) & 15) == 0 && (((uintptr_t)g + gsz * h) & 15) == 0 &&
+        (((uintptr_t)m + esz * h) & 15) == 0 && (((uintptr_t)v + esz * h) & 15) == 0) { head = h < n ? h : n; break; }
+  const long groups = (n - head) >> 3, nscalar = n - (groups << 3);
+  dim3 grid(grid_for(groups > nscalar ? groups : nscalar)), blk(256);
+  const float* hy = (const float*)hyper; const float* cf = (const float*)coef;
+  bf16_t* pb = (bf16_t*)p; float* wf = (float*)w;
+  if (mdtype == 0 && gdtype == 0)
+    az_launch((adamw_master_kernel<bf16_t, bf16_t>), grid, blk, 0, st, n, pb, wf, (const bf16_t*)g, (bf16_t*)m, (bf16_t*)v, hy, cf, head, groups);
+  else if (mdtype == 1 && gdtype == 0)
+    az_launch((adamw_master_kernel<float, bf16_t>), grid, blk, 0, st, n, pb, wf, (const bf16_t*)g, (float*)m, (float*)v, hy, cf, head, groups);
+  else if (mdtype == 0 && gdtype == 1)
+    az_launch((adamw_master_kernel<bf16_t, float>), grid, blk, 0, st, n, pb, wf, (const float*)g, (bf16_t*)m, (bf16_t*)v, hy, cf, head, groups);
+  else if (mdtype == 1 && gdtype == 1)
+    az_launch((adamw_master_kernel<float, float>), grid, blk, 0, st, n, pb, wf, (const float*)g, (float*)m, (float*)v, hy, cf, head, groups);
+  else if (mdtype == 2 && gdtype == 0)
+    az_launch((adamw_master_kernel<f16_t, bf16_t>), grid, blk, 0, st, n, pb, wf, (const bf16_t*)g, (f16_t*)m, (f16_t*)v, hy, cf, head, groups);
+  else
+    az_launch((adamw_master_kernel<f16_t, float>), grid, blk, 0, st, n, pb, wf, (const float*)g, (f16_t*)m, (f16_t*)v, hy, cf, head, groups);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+
 // Hand-off events of the chunk pipeline, one set per COMPUTE STREAM (a stream belongs to one device, so two optimizers,
 // threads or devices in one process never share a set); creation is serialised by a mutex.  Calls that name the same
 // compute stream must come from one host thread at a time -- the stream's own order is what sequences them.
@@ -483,6 +547,16 @@ int az_ema_flat(long n, const void* p, void* ema_f32, float one_minus_decay, voi
             (float*)ema_f32, one_minus_decay, head, groups);
   AZ_CHECK_LAUNCH();
   return AZ_OK;
+}
+
+int az_adamw_flat_master(long n, void* p, void* w_f32, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper,
+                         const void* coef, void* stream) {
+  if (n < 0 || !p || !w_f32 || !g || !m || !v || !hyper || mdtype < 0 || mdtype > 2 || gdtype < 0 || gdtype > 1) return AZ_ERR_ARG(76);
+  const uintptr_t emask = mdtype == 1 ? 3 : 1, gmask = gdtype == 0 ? 1 : 3;
+  if (((uintptr_t)p & 1) || ((uintptr_t)w_f32 & 3) || ((uintptr_t)g & gmask) || ((uintptr_t)m & emask) || ((uintptr_t)v & emask))
+    return AZ_ERR_ARG(77);
+  if (n == 0) return AZ_OK;
+  return launch_adamw_master(n, p, w_f32, g, gdtype, m, v, mdtype, hyper, coef, (hipStream_t)stream);
 }
 
 int az_raven_step_ex(long n, void* p, const void* g, int gdtype, void* m_host, void* v_host, int mdtype, const void* hyper,

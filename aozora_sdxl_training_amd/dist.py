@@ -38,6 +38,8 @@ from . import ops
 from ._lib import lib
 
 _MD = {torch.bfloat16: 0, torch.float32: 1, torch.float16: 2}
+MASTER_SR_REFUSAL = ("master_weights and stochastic_rounding do not combine: stochastic rounding exists because there is no fp32 master "
+                     "copy -- with one, the bf16 parameters are its round-to-nearest image; choose one of the two")
 
 
 # ---- backend-agnostic flat collectives (nccl = RCCL in production; gloo in tests) -----------------
@@ -114,13 +116,19 @@ class ShardedRaven:
 
     ema (not in the reference, None = off): an ema.EmaWeights that tracks exactly this optimizer's owned trainable elements, or
     dict(decay=, warmup=) from which that shard is built here, in the layout of m_dev / v_dev (the owned ranges exist only now); either
-    way it is `self.ema`, and step() issues its launches on the streams that update each range."""
+    way it is `self.ema`, and step() issues its launches on the streams that update each range.
+
+    master_weights (not in the reference, False = off): `self.w_dev`, one fp32 device buffer in the layout of m_dev / v_dev, holds the
+    master copy of this rank's owned trainable elements; the update reads and writes it and pflat receives bf16(master)
+    (az_adamw_flat_master; INTEGRATION.md "fp32 master weights").  Whoever writes parameters from outside calls resync_master()."""
 
     def __init__(self, unet, lr=8e-7, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, debias_strength=0.3,
                  momentum_dtype=torch.bfloat16, clip_grad_norm=1.0, process_group=None, force_local=False,
                  overlap=True, regions: Optional[int] = None, force_exchange=False, state_on_host=False,
-                 stochastic_rounding: bool = False, sr_seed: int = 0, ema=None):
+                 stochastic_rounding: bool = False, sr_seed: int = 0, ema=None, master_weights: bool = False):
         import torch.distributed as dist
+        if master_weights and stochastic_rounding:
+            raise ValueError(MASTER_SR_REFUSAL)
         self.unet = unet
         # stochastic rounding of the bf16 write-back (not in the reference, off by default: optimizers.RavenAdamW): the random bits are
         # keyed by (sr_seed, step_count, offset in the flat buffer), so regions, rank shards and RavenAdamW's ranges all draw the same
@@ -185,6 +193,14 @@ class ShardedRaven:
             self.m_host = self.v_host = None
             self.m_dev = torch.zeros(max(own_n, 1), dtype=momentum_dtype, device=dev)
             self.v_dev = torch.zeros(max(own_n, 1), dtype=momentum_dtype, device=dev)
+        # fp32 master copy of the owned trainable elements (not in the reference, off = None: no launch, allocation or event differs):
+        # packed like m_dev / v_dev, 4 B per owned trainable element, resident in HBM whatever state_on_host says -- the moments are
+        # staged into m_dev / v_dev before the update either way.  float32(bf16) is exact.
+        self.master = bool(master_weights)
+        self.w_dev = None
+        if self.master:
+            self.w_dev = torch.empty(own_n, dtype=torch.float32, device=dev)
+            self._fill_master()
         self._h2d_done = None
         self._d2h_done = None
         self._prefetched = False
@@ -219,6 +235,52 @@ class ShardedRaven:
             for a, b in rs:
                 ema.offset_of(a, b)            # ValueError: an owned range the EMA does not track
         return ema
+
+    # ---- fp32 master weights ---------------------------------------------------------------------
+    def _owned(self):
+        """(a, b, offset in the packed state buffers) of every owned trainable range."""
+        return [(a, b, o) for rs, offs in zip(self.ranges, self.range_off) for (a, b), o in zip(rs, offs)]
+
+    def _fill_master(self):
+        for a, b, o in self._owned():
+            self.w_dev[o:o + (b - a)].copy_(self.unet.pflat[a:b])
+
+    def _need_master(self):
+        if self.w_dev is None:
+            raise ValueError("this optimizer keeps no fp32 master weights (master_weights=False)")
+
+    def resync_master(self):
+        """master <- float32(pflat) over the owned ranges, once every update in flight has landed: for whoever writes parameters from
+        outside (unet.load_state_dict, ema.copy_to) -- the next step would otherwise overwrite them with bf16(old master + update)."""
+        self._need_master()
+        self.synchronize_state()
+        self._fill_master()
+        torch.cuda.synchronize(self.unet.device)
+
+    def save_master_state(self):
+        """This rank's master copy and the layout it belongs to -> {world, rank, ranges, master (host fp32)}."""
+        self._need_master()
+        self.synchronize_state()
+        return {"world": self.world, "rank": self.rank, "ranges": [list(map(tuple, rs)) for rs in self.ranges], "master": self.w_dev.cpu()}
+
+    def load_master_state(self, st):
+        self._need_master()
+        for key, mine in (("world", self.world), ("rank", self.rank)):
+            if st.get(key) != mine:
+                raise ValueError(f"master-weight state was written with {key} = {st.get(key)}, this run has {key} = {mine}")
+        theirs, mine = [list(map(tuple, rs)) for rs in st.get("ranges", [])], [list(map(tuple, rs)) for rs in self.ranges]
+        if len(theirs) != len(mine):
+            raise ValueError(f"master-weight state was written with {len(theirs)} region(s), this run has {len(mine)}: another region layout")
+        if theirs != mine:
+            raise ValueError("master-weight state covers other owned trainable ranges than this run: the freeze mask (or the region "
+                             "layout) changed")
+        w = st.get("master")
+        if not torch.is_tensor(w) or w.dtype != torch.float32 or w.numel() != self.w_dev.numel():
+            raise ValueError(f"master-weight state holds {'no fp32 tensor' if not torch.is_tensor(w) or w.dtype != torch.float32 else str(w.numel()) + ' elements'}"
+                             f", this run owns {self.w_dev.numel()} trainable elements")
+        self.synchronize_state()
+        self.w_dev.copy_(w.reshape(-1))
+        torch.cuda.synchronize(self.unet.device)
 
     def _ema_regions(self, regions, stream):
         """EMA launches of the owned ranges of `regions` on `stream` (the stream that updated them); no EMA: nothing."""
@@ -373,6 +435,12 @@ class ShardedRaven:
             sp = ctypes.c_void_p(stream.cuda_stream)
             for k, (a, b) in enumerate(self.ranges[i]):
                 hoff = self.range_off[i][k]
+                if self.master:
+                    L.call("az_adamw_flat_master", b - a, ctypes.c_void_p(u.pflat.data_ptr() + a * 2), ctypes.c_void_p(self.w_dev.data_ptr() + hoff * 4),
+                           ctypes.c_void_p(u.gflat.data_ptr() + a * 2), 0,
+                           ctypes.c_void_p(self.m_dev.data_ptr() + hoff * esz), ctypes.c_void_p(self.v_dev.data_ptr() + hoff * esz),
+                           _MD[self.mdt], ctypes.c_void_p(self.hyper_dev.data_ptr()), ctypes.c_void_p(self.scal[1:2].data_ptr()), sp)
+                    continue
                 if self.sr:
                     L.call("az_adamw_flat_sr", b - a, ctypes.c_void_p(u.pflat.data_ptr() + a * 2), ctypes.c_void_p(u.gflat.data_ptr() + a * 2), 0,
                            ctypes.c_void_p(self.m_dev.data_ptr() + hoff * esz), ctypes.c_void_p(self.v_dev.data_ptr() + hoff * esz),
@@ -396,7 +464,7 @@ class ShardedRaven:
             with torch.cuda.stream(bg):
                 later = []
                 for i in (1, 2):
-                    with self._span(f"update_region{i}", bg, 14 * sum(b - a for a, b in self.ranges[i])):
+                    with self._span(f"update_region{i}", bg, (20 if self.master else 14) * sum(b - a for a, b in self.ranges[i])):
                         update_region(i, bg)
                     ev = torch.cuda.Event(); ev.record(bg)
                     later.append((i, ev))
@@ -634,6 +702,8 @@ class ShardedRaven:
             self._d2h_done.synchronize()
         if self.ema is not None:
             self.ema.synchronize()
+        if self.w_dev is not None:           # the master is resident: written by every stream that updates a region
+            torch.cuda.synchronize(self.unet.device)
 
 
 class ShardedTitan(ShardedRaven):
@@ -751,6 +821,12 @@ class ShardedTitan(ShardedRaven):
         for i, rs in enumerate(self.ranges):
             for k, (a, b) in enumerate(rs):
                 hoff = self.range_off[i][k]
+                if self.master:
+                    L.call("az_adamw_flat_master", b - a, ctypes.c_void_p(u.pflat.data_ptr() + a * 2), ctypes.c_void_p(self.w_dev.data_ptr() + hoff * 4),
+                           ctypes.c_void_p(self.gacc.data_ptr() + a * 4), 1,
+                           ctypes.c_void_p(self.m_dev.data_ptr() + hoff * esz), ctypes.c_void_p(self.v_dev.data_ptr() + hoff * esz),
+                           _MD[self.mdt], ctypes.c_void_p(self.hyper_dev.data_ptr()), ctypes.c_void_p(self.scal[1:2].data_ptr()), st)
+                    continue
                 if self.sr:
                     L.call("az_adamw_flat_sr", b - a, ctypes.c_void_p(u.pflat.data_ptr() + a * 2), ctypes.c_void_p(self.gacc.data_ptr() + a * 4), 1,
                            ctypes.c_void_p(self.m_dev.data_ptr() + hoff * esz), ctypes.c_void_p(self.v_dev.data_ptr() + hoff * esz),

@@ -683,3 +683,25 @@ def ema_flat(p, ema, one_minus_decay, stream=None):
         return
     st = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
     lib().call("az_ema_flat", p.numel(), _ptr(p), _ptr(ema), float(one_minus_decay), st)
+
+
+_MOMENT_CODE = {BF16: 0, F32: 1, torch.float16: 2}
+
+
+def adamw_flat_master(p, w, g, m, v, hyper, coef=None, stream=None):
+    """The Raven / Titan AdamW update with an fp32 master copy: w (fp32, read and written) is the parameter operand, p (bf16) receives
+    bf16(w) and is never read; g bf16 or fp32, m / v bf16, fp32 or fp16, hyper the fp32 vector of az_adamw_flat, coef None or a device
+    fp32 scalar.  All 1-D, contiguous, of one length, on `stream` (default: the current one).  An empty range launches nothing."""
+    ts = (p, w, g, m, v)
+    _req(all(t.is_cuda and t.device == p.device for t in ts + (hyper,)) and (coef is None or (coef.is_cuda and coef.device == p.device)),
+         "adamw_flat_master needs cuda tensors on one device")
+    _req(p.dtype == BF16 and w.dtype == F32 and g.dtype in (BF16, F32) and m.dtype in _MOMENT_CODE and v.dtype == m.dtype,
+         "adamw_flat_master needs bf16 p, fp32 w, bf16 / fp32 g and bf16 / fp32 / fp16 moments of one type")
+    _req(all(t.dim() == 1 and t.is_contiguous() and t.numel() == p.numel() for t in ts), "adamw_flat_master shapes")
+    _req(hyper.dtype == F32 and hyper.is_contiguous() and hyper.numel() >= 7, "adamw_flat_master needs the fp32 hyper vector of 7+ entries")
+    _req(coef is None or (coef.dtype == F32 and coef.numel() >= 1), "adamw_flat_master needs an fp32 clip coefficient")
+    if p.numel() == 0:             # (an empty tensor has no address to hand over)
+        return
+    st = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    lib().call("az_adamw_flat_master", p.numel(), _ptr(p), _ptr(w), _ptr(g), int(g.dtype == F32), _ptr(m), _ptr(v), _MOMENT_CODE[m.dtype],
+               _ptr(hyper), _ptr(coef), st)

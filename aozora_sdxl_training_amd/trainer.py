@@ -32,6 +32,12 @@ _RAVEN_DEFAULTS = dict(betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, debias_s
 _ADAMW8_DEFAULTS = dict(betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)      # config.py PAGED_ADAMW_8BIT_PARAMS
 _SR_8BIT_REFUSAL = ("stochastic_rounding is an option of raven and titan (RAVEN_PARAMS / TITAN_PARAMS): paged_adamw_8bit writes its "
                     "parameters through two roundings of its own, a different contract -- remove the key from PAGED_ADAMW_8BIT_PARAMS")
+_MASTER_8BIT_REFUSAL = ("master_weights is an option of raven and titan (RAVEN_PARAMS / TITAN_PARAMS): paged_adamw_8bit has no fp32 master "
+                        "copy -- remove the key from PAGED_ADAMW_8BIT_PARAMS")
+_MASTER_SR_REFUSAL = ("master_weights and stochastic_rounding do not combine: stochastic rounding exists because there is no fp32 master "
+                      "copy -- with one, the bf16 parameters are its round-to-nearest image; set one of the two keys")
+_MASTER_HOST_TITAN_REFUSAL = ("master_weights does not combine with TITAN_HOST_GRADIENTS = true: that path runs the drop-in "
+                              "optimizers.TitanAdamW (fp32 gradients in pinned host memory), which keeps no master copy -- drop one of the two")
 _ADAMW8_DP_REFUSAL = "paged_adamw_8bit runs at one rank only: data-parallel training supports raven and titan"
 
 
@@ -75,6 +81,29 @@ def _sr_args(config, hp):
     return dict(stochastic_rounding=on, sr_seed=int(getattr(config, "SEED", 0) or 0))
 
 
+def _as_bool(v):
+    return v.strip().lower() in ("true", "1", "t", "y", "yes") if isinstance(v, str) else bool(v)      # config.coerce_types' reading of a bool
+
+
+def _master_option(config) -> bool:
+    """"master_weights": true in RAVEN_PARAMS / TITAN_PARAMS (absent = false; not in the reference): an fp32 master copy of the trainable
+    weights in the flat optimizers (dist.ShardedRaven / ShardedTitan; INTEGRATION.md "fp32 master weights").  Refuses, before anything
+    is allocated, what it does not combine with: the 8-bit optimizer, stochastic rounding, Titan with host gradients."""
+    kind = str(getattr(config, "OPTIMIZER_TYPE", "raven")).lower()
+    if kind == "paged_adamw_8bit":
+        if "master_weights" in dict(getattr(config, "PAGED_ADAMW_8BIT_PARAMS", {}) or {}):
+            raise ValueError(_MASTER_8BIT_REFUSAL)
+        return False
+    hp = dict(getattr(config, "TITAN_PARAMS" if kind == "titan" else "RAVEN_PARAMS", {}) or {})
+    if not _as_bool(hp.get("master_weights", False)):
+        return False
+    if _as_bool(hp.get("stochastic_rounding", False)):
+        raise ValueError(_MASTER_SR_REFUSAL)
+    if kind == "titan" and bool(getattr(config, "TITAN_HOST_GRADIENTS", False)):
+        raise ValueError(_MASTER_HOST_TITAN_REFUSAL)
+    return True
+
+
 def _optimizer_8bit(config, params):
     """create_optimizer (train.py:2271-2288): PagedAdamW8bit from PAGED_ADAMW_8BIT_PARAMS at lr = max(curve), min_8bit_size 4096."""
     curve = getattr(config, "LR_CUSTOM_CURVE", [])
@@ -82,6 +111,8 @@ def _optimizer_8bit(config, params):
     hp = {**_ADAMW8_DEFAULTS, **dict(getattr(config, "PAGED_ADAMW_8BIT_PARAMS", {}) or {})}
     if "stochastic_rounding" in hp:
         raise ValueError(_SR_8BIT_REFUSAL)
+    if "master_weights" in hp:
+        raise ValueError(_MASTER_8BIT_REFUSAL)
     return PagedAdamW8bit(params, lr=lr, betas=tuple(hp["betas"]), eps=hp["eps"], weight_decay=hp["weight_decay"], min_8bit_size=4096)
 
 
@@ -102,19 +133,20 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     # "ema_decay" [, "ema_warmup"] in the ACTIVE optimizer's dictionary: an fp32 EMA of the trainable weights (ema.py; not in the
     # reference, absent = off).  Read first: an invalid value is refused before anything is allocated.
     ema_decay, ema_warmup = _ema_options(getattr(config, {"titan": "TITAN_PARAMS", "paged_adamw_8bit": "PAGED_ADAMW_8BIT_PARAMS"}.get(kind, "RAVEN_PARAMS"), None))
+    master = _master_option(config)          # "master_weights" (not in the reference, absent = off); refusals before anything is allocated
     GA = int(config.GRADIENT_ACCUMULATION_STEPS)
     mode = getattr(config, "PREDICTION_TYPE", "epsilon")
     config.is_rectified_flow = (mode == "rectified_flow")
     micro_step = optimizer_step = 0
     model_to_load = Path(config.SINGLE_FILE_CHECKPOINT_PATH)
     sampler_seed, optimizer_state, ts_state = config.SEED, None, None
-    ema_saved = None
+    ema_saved = master_saved = None
     if getattr(config, "RESUME_TRAINING", False):                                   # train.py:2558-2573
         rs = ckpt.load_training_state(config.RESUME_STATE_PATH, GA)
         micro_step, optimizer_step = rs["micro_step"], rs["optimizer_step"]
         sampler_seed, ts_state, optimizer_state = rs["sampler_seed"], rs["timestep_sampler_state"], rs["optimizer_state"]
         model_to_load = Path(config.RESUME_MODEL_PATH)
-        ema_saved = rs["raw"].get("ema_state")
+        ema_saved, master_saved = rs["raw"].get("ema_state"), rs["raw"].get("master_state")
         ckpt.restore_rng(rs["raw"])
     if unet is None:
         unet = ckpt.load_unet(model_to_load, device)
@@ -155,13 +187,16 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
             # m / v stay resident in HBM (10.3 GB of 288) unless the preset asks for the reference's residency -- pinned host memory,
             # streamed over the host link every optimizer step (raven.py:83-84, 114-117) -- with RAVEN_STATE_ON_HOST = true
             state_on_host=bool(getattr(config, "RAVEN_STATE_ON_HOST", False)), **_sr_args(config, hp),
-            ema=dict(decay=ema_decay, warmup=ema_warmup) if ema_decay is not None else None)
+            ema=dict(decay=ema_decay, warmup=ema_warmup) if ema_decay is not None else None, **(dict(master_weights=True) if master else {}))
     else:
         optimizer = _optimizer(config, params)
     if rank == 0 and getattr(optimizer, "sr", getattr(optimizer, "_sr", False)):
         print(f"INFO: stochastic rounding of the bf16 parameter update is ON (seed {int(getattr(config, 'SEED', 0) or 0)}): an option outside "
               "the reference; results differ from the default round-to-nearest write-back")
     flat_opt = isinstance(optimizer, ShardedRaven)
+    if rank == 0 and master:
+        print(f"INFO: fp32 master weights are ON ({optimizer.w_dev.numel() * 4} bytes of fp32 on this rank): an option outside the reference; "
+              "results differ from the default bf16-only update from the second optimizer step on")
     # the flat optimizers issue the EMA launches themselves, on the streams that update each range; a module optimizer's step() is
     # followed by ema.update() in the loop
     ema = None if ema_decay is None else (optimizer.ema if flat_opt else EmaWeights(unet, ema_decay, ema_warmup))
@@ -172,7 +207,7 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     if getattr(config, "RESUME_TRAINING", False):
         if dp:       # every rank resumes its own shard (written next to rank 0's training-state file)
             shard = torch.load(str(config.RESUME_STATE_PATH) + f".rank{rank}", map_location="cpu", weights_only=False)
-            ema_saved = shard.get("ema_state")
+            ema_saved, master_saved = shard.get("ema_state"), shard.get("master_state")
             ckpt.resume_optimizer(optimizer, shard, lr_scheduler, micro_step)
         else:
             ckpt.resume_optimizer(optimizer, optimizer_state, lr_scheduler, micro_step)
@@ -182,6 +217,14 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
             print("INFO: the training state holds no EMA (\"ema_state\"): the EMA starts from the loaded parameters with k = 0")
         elif ema_saved is not None and rank == 0:
             print("INFO: the training state holds an EMA (\"ema_state\") but \"ema_decay\" is not set: ignored")
+        if master and master_saved is not None:
+            optimizer.load_master_state(master_saved)
+            if rank == 0:
+                print("INFO: fp32 master weights restored from the training state (\"master_state\")")
+        elif master and rank == 0:
+            print("INFO: the training state holds no fp32 master weights (\"master_state\"): the master starts from the loaded parameters")
+        elif master_saved is not None and rank == 0:
+            print("INFO: the training state holds fp32 master weights (\"master_state\") but \"master_weights\" is not set: ignored")
 
     dataset = feed.CachedLatentDataset(config)
     timestep_sampler = TimestepSampler(config)
@@ -393,6 +436,8 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
                         # EMA: every rank takes part in the gather (state_dict) and keeps its own fp32 shard; rank 0 writes the file
                         ema_sd = ema.state_dict() if ema is not None else None
                         ema_extra = {"ema_state": ema.save_state()} if ema is not None else None
+                        if master:               # this rank's fp32 master shard travels with the training state, like the EMA's
+                            ema_extra = {**(ema_extra or {}), "master_state": optimizer.save_master_state()}
                         if dp:
                             Path(config.OUTPUT_DIR).mkdir(parents=True, exist_ok=True)
                             torch.save({**optimizer.save_cpu_state(), **(ema_extra or {})}, str(Path(config.OUTPUT_DIR) / sname) + f".rank{rank}")

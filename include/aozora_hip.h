@@ -391,6 +391,17 @@ int az_raven_step_sr(long n, void* p, const void* g, int gdtype, void* m_host, v
  * returns 0 without a launch; n < 0, a null pointer, p not 2-byte aligned or e not 4-byte aligned are argument errors. */
 /* ref: not in the reference; runs behind `optimizer.step()`, train.py:2783 */
 int az_ema_flat(long n, const void* p, void* ema_f32, float one_minus_decay, void* stream);
+/* AdamW over a flat range with an fp32 MASTER copy of the parameters (an option the reference does not have; off by default --
+ * INTEGRATION.md "fp32 master weights"): the arithmetic of az_adamw_flat_ex operation for operation (the reference's order, no
+ * contraction, the clip coefficient applied in-kernel, a bf16 gradient rounded to bf16 after the multiplication) with ONE difference:
+ * the parameter operand is w[i] (fp32, read) instead of float(p[i]).  Writes w[i] = pp and p[i] = bf16(pp), round to nearest even; p
+ * is never read.  m, v, mdtype, gdtype, hyper and coef (may be null) as az_adamw_flat_ex.  NaN and inf follow IEEE rules through both
+ * outputs.  16-byte accesses from the first element at which p, g, m, v and w are all 16-byte aligned, element-wise before it, in the
+ * tail, and everywhere when the five cannot be co-aligned.  n == 0 returns 0 without a launch; n < 0, a null p / w / g / m / v / hyper,
+ * mdtype or gdtype out of range, or a pointer not aligned to its element (p 2 bytes, w 4 bytes) are argument errors. */
+/* ref: raven.py:109-147 (the update with p32 kept between steps instead of p.copy_(p32) alone), titan.py:230-296 */
+int az_adamw_flat_master(long n, void* p, void* w_f32, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper,
+                         const void* coef, void* stream);
 /* g_bf16[i] = bf16(g[i] * coef[0]) in place -- the in-place clip of torch.nn.utils.clip_grad_norm_
  * (train.py:2775-2778); skipped entirely when coef[0] == 1 */
 /* ref: train.py:2775-2778 (in-place gradient scaling of clip_grad_norm_) */
