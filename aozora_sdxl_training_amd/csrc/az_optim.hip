@@ -3,6 +3,7 @@
 // with first/second moments resident in PINNED HOST memory, streamed through the GPU by async copies.
 #include "az_common.h"
 #include "aozora_hip.h"
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <type_traits>
@@ -85,8 +86,10 @@ struct SrArgs {
   uint32_t k0, k1;     // key: seed low / high word
   uint32_t step, dom;  // counter words 2, 3
   long elem0;          // global index of the call's first element; counter words 0, 1 = (elem0 + i) >> 3
-  long head, groups;   // [0, head) scalar, then `groups` aligned groups of 8 (16-byte accesses), then the scalar tail up to n
 };
+// How the wide kernels walk a range of n elements: [0, head) scalar, then `groups` aligned groups of 8 (16-byte accesses), then the
+// scalar tail up to n (split_for)
+struct Split { long head, groups; };
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
 #pragma unroll
@@ -145,19 +148,19 @@ __device__ __forceinline__ void adamw_math(const AdamwK& k, LG ldg, LM ldm, LV l
   pp = pp + ((-k.step * mm) / denom);
 }
 
-// Element i of the range through memory.  SR: r16 = the element's 16 random bits; otherwise round to nearest even (raven.py:144).
-template <typename TM, typename TG, bool SR>
-__device__ __forceinline__ void adamw_elem(const AdamwK& k, long i, bf16_t* __restrict__ p, const TG* __restrict__ g, TM* __restrict__ m,
-                                           TM* __restrict__ v, uint32_t r16) {
+// Element i of the range through memory; the parameter operand is read by ldp() and written by stp(pp) (raven.py:144: bf16, round to
+// nearest even, in the default kernel).
+template <typename TM, typename TG, typename LP, typename SP>
+__device__ __forceinline__ void adamw_elem(const AdamwK& k, long i, const TG* __restrict__ g, TM* __restrict__ m, TM* __restrict__ v, LP ldp,
+                                           SP stp) {
   float mm, vv, pp;
-  adamw_math<TG>(k, [&] { return ldf<TG>(g, i); }, [&] { return ldf<TM>(m, i); }, [&] { return ldf<TM>(v, i); }, [&] { return bf2f(p[i]); },
-                 mm, vv, pp);
-  if constexpr (SR) p[i] = sr_round(pp, r16); else p[i] = f2bf(pp);
+  adamw_math<TG>(k, [&] { return ldf<TG>(g, i); }, [&] { return ldf<TM>(m, i); }, [&] { return ldf<TM>(v, i); }, ldp, mm, vv, pp);
+  stp(pp);
   stf<TM>(m, i, mm);
   stf<TM>(v, i, vv);
 }
 
-// 8 consecutive elements <-> registers with 16-byte accesses (the pointer is 16-byte aligned: launch_adamw_sr)
+// 8 consecutive elements <-> registers with 16-byte accesses (the pointer is 16-byte aligned: split_for)
 template <typename T> __device__ __forceinline__ void load8(const T* __restrict__ q, float* x) {
   if constexpr (sizeof(T) == 4) {
     const float4 a = reinterpret_cast<const float4*>(q)[0], b = reinterpret_cast<const float4*>(q)[1];
@@ -197,42 +200,64 @@ __global__ void adamw_kernel(long n, bf16_t* __restrict__ p, const TG* __restric
                              const float* __restrict__ hyper, const float* __restrict__ coef) {
   const AdamwK k = adamw_consts(hyper, coef);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    adamw_elem<TM, TG, false>(k, i, p, g, m, v, 0u);
+    adamw_elem<TM, TG>(k, i, g, m, v, [&] { return bf2f(p[i]); }, [&](float pp) { p[i] = f2bf(pp); });
 }
 
-// az_adamw_flat_sr: the same element update, p written with stochastic rounding.  One thread per aligned group of 8 elements (one
-// Philox evaluation, 16-byte accesses to p, g, m, v); the scalar head [0, head) and the tail behind the last whole group evaluate
-// their group's Philox word per element.
-template <typename TM, typename TG>
-__global__ void adamw_sr_kernel(long n, bf16_t* __restrict__ p, const TG* __restrict__ g, TM* __restrict__ m, TM* __restrict__ v,
-                                const float* __restrict__ hyper, const float* __restrict__ coef, SrArgs sr) {
-  const AdamwK k = adamw_consts(hyper, coef);
-  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long)gridDim.x * blockDim.x;
-  const long body = sr.head + (sr.groups << 3);             // <= n (launch_adamw_sr)
-  for (long gi = tid; gi < sr.groups; gi += nthr) {
-    const long i = sr.head + (gi << 3);                     // (elem0 + i) & 7 == 0
-    uint32_t w[4];
+// The parameter operand of the wide kernel is a policy P, passed by value: read 8 / read 1 / write 8 / write 1 at element i.
+// SrParam (az_adamw_flat_sr): bf16 p written with stochastic rounding -- one Philox evaluation per aligned group of 8 ((elem0 + i) & 7
+// == 0 there); a scalar element evaluates its group's word for itself.
+struct SrParam {
+  bf16_t* p;
+  SrArgs sr;
+  __device__ __forceinline__ void load8(long i, float* x) const { ::load8<bf16_t>(p + i, x); }
+  __device__ __forceinline__ float load(long i) const { return bf2f(p[i]); }
+  __device__ __forceinline__ void store8(long i, const float* x) const {
+    uint32_t w[4], o[4];
     sr_group_bits(sr, (sr.elem0 + i) >> 3, w);
-    float gg[8], mm[8], vv[8], pp[8];
-    load8<TG>(g + i, gg); load8<TM>(m + i, mm); load8<TM>(v + i, vv); load8<bf16_t>(p + i, pp);
 #pragma unroll
-    for (int e = 0; e < 8; ++e)
-      adamw_math<TG>(k, [&] { return gg[e]; }, [&] { return mm[e]; }, [&] { return vv[e]; }, [&] { return pp[e]; }, mm[e], vv[e], pp[e]);
-    uint32_t o[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      o[e] = (uint32_t)sr_round(pp[2 * e], w[e] & 0xFFFFu) | ((uint32_t)sr_round(pp[2 * e + 1], w[e] >> 16) << 16);
+    for (int e = 0; e < 4; ++e) o[e] = (uint32_t)sr_round(x[2 * e], w[e] & 0xFFFFu) | ((uint32_t)sr_round(x[2 * e + 1], w[e] >> 16) << 16);
     reinterpret_cast<uint4*>(p + i)[0] = make_uint4(o[0], o[1], o[2], o[3]);
-    store8_moment<TM>(m + i, mm);
-    store8_moment<TM>(v + i, vv);
   }
-  const long nscalar = n - (sr.groups << 3);                 // head + tail
-  for (long j = tid; j < nscalar; j += nthr) {
-    const long i = j < sr.head ? j : j - sr.head + body;
+  __device__ __forceinline__ void store(long i, float x) const {
     const long e = sr.elem0 + i;
     uint32_t w[4];
     sr_group_bits(sr, e >> 3, w);
-    adamw_elem<TM, TG, true>(k, i, p, g, m, v, sr_lane_bits(w, (int)(e & 7)));
+    p[i] = sr_round(x, sr_lane_bits(w, (int)(e & 7)));
+  }
+};
+// MasterParam (az_adamw_flat_master; INTEGRATION.md "fp32 master weights"): the fp32 master w is the operand; writes w = pp and p =
+// bf16(pp), round to nearest even -- p is never read.
+struct MasterParam {
+  bf16_t* p;
+  float* w;
+  __device__ __forceinline__ void load8(long i, float* x) const { ::load8<float>(w + i, x); }
+  __device__ __forceinline__ float load(long i) const { return w[i]; }
+  __device__ __forceinline__ void store8(long i, const float* x) const { store8_moment<float>(w + i, x); store8_moment<bf16_t>(p + i, x); }
+  __device__ __forceinline__ void store(long i, float x) const { w[i] = x; p[i] = f2bf(x); }
+};
+
+// The element update over the split s: one thread per aligned group of 8 (16-byte accesses), head and tail one element per thread.
+template <typename TM, typename TG, typename P>
+__global__ void adamw_wide_kernel(long n, P par, const TG* __restrict__ g, TM* __restrict__ m, TM* __restrict__ v,
+                                  const float* __restrict__ hyper, const float* __restrict__ coef, Split s) {
+  const AdamwK k = adamw_consts(hyper, coef);
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long)gridDim.x * blockDim.x;
+  const long body = s.head + (s.groups << 3);               // <= n (split_for)
+  for (long gi = tid; gi < s.groups; gi += nthr) {
+    const long i = s.head + (gi << 3);
+    float gg[8], mm[8], vv[8], pp[8];
+    load8<TG>(g + i, gg); load8<TM>(m + i, mm); load8<TM>(v + i, vv); par.load8(i, pp);
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      adamw_math<TG>(k, [&] { return gg[e]; }, [&] { return mm[e]; }, [&] { return vv[e]; }, [&] { return pp[e]; }, mm[e], vv[e], pp[e]);
+    par.store8(i, pp);
+    store8_moment<TM>(m + i, mm);
+    store8_moment<TM>(v + i, vv);
+  }
+  const long nscalar = n - (s.groups << 3);                  // head + tail
+  for (long j = tid; j < nscalar; j += nthr) {
+    const long i = j < s.head ? j : j - s.head + body;
+    adamw_elem<TM, TG>(k, i, g, m, v, [&] { return par.load(i); }, [&](float pp) { par.store(i, pp); });
   }
 }
 
@@ -264,60 +289,65 @@ inline int grid_for(long n) {
   return (int)g;
 }
 
-int launch_adamw(long n, void* p, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper, const void* coef,
+// The split of a range over the operands `ptrs`: head = the first h in [0, 8) at which every pointer is 16-byte aligned -- with
+// forced >= 0 that h or nothing; none, or beyond the range: every element takes the scalar form.
+struct Operand { const void* ptr; size_t esz; };
+inline Split split_for(long n, std::initializer_list<Operand> ptrs, long forced = -1) {
+  long head = n;
+  for (long h = forced < 0 ? 0 : forced, end = forced < 0 ? 8 : forced + 1; h < end; ++h) {
+    bool aligned = true;
+    for (const Operand& o : ptrs) aligned = aligned && (((uintptr_t)o.ptr + o.esz * h) & 15) == 0;
+    if (aligned) { head = h < n ? h : n; break; }
+  }
+  return Split{head, (n - head) >> 3};
+}
+inline int grid_for(long n, Split s) {
+  const long nscalar = n - (s.groups << 3);
+  return grid_for(s.groups > nscalar ? s.groups : nscalar);
+}
+
+// (mdtype, gdtype) -> f(moment type tag, gradient type tag); false: no such pair, f was not called
+template <typename T> struct Tag { typedef T type; };
+template <typename F> bool adamw_dispatch(int mdtype, int gdtype, F f) {
+  if (gdtype < 0 || gdtype > 1) return false;
+  auto with_g = [&](auto tm) { if (gdtype == 0) f(tm, Tag<bf16_t>()); else f(tm, Tag<float>()); };
+  if (mdtype == 0) with_g(Tag<bf16_t>());
+  else if (mdtype == 1) with_g(Tag<float>());
+  else if (mdtype == 2) with_g(Tag<f16_t>());
+  else return false;
+  return true;
+}
+
+// par = the bf16 parameter pointer (the default kernel, s unused) or a policy of the wide kernel
+template <typename P>
+int launch_adamw(long n, P par, Split s, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper, const void* coef,
                  hipStream_t st) {
-  dim3 grid(grid_for(n)), blk(256);
+  constexpr bool wide = !std::is_pointer<P>::value;
+  dim3 grid(wide ? grid_for(n, s) : grid_for(n)), blk(256);
   const float* hy = (const float*)hyper; const float* cf = (const float*)coef;
-  if (mdtype == 0 && gdtype == 0)
-    az_launch((adamw_kernel<bf16_t, bf16_t>), grid, blk, 0, st, n, (bf16_t*)p, (const bf16_t*)g, (bf16_t*)m, (bf16_t*)v, hy, cf);
-  else if (mdtype == 1 && gdtype == 0)
-    az_launch((adamw_kernel<float, bf16_t>), grid, blk, 0, st, n, (bf16_t*)p, (const bf16_t*)g, (float*)m, (float*)v, hy, cf);
-  else if (mdtype == 0 && gdtype == 1)
-    az_launch((adamw_kernel<bf16_t, float>), grid, blk, 0, st, n, (bf16_t*)p, (const float*)g, (bf16_t*)m, (bf16_t*)v, hy, cf);
-  else if (mdtype == 1 && gdtype == 1)
-    az_launch((adamw_kernel<float, float>), grid, blk, 0, st, n, (bf16_t*)p, (const float*)g, (float*)m, (float*)v, hy, cf);
-  else if (mdtype == 2 && gdtype == 0)
-    az_launch((adamw_kernel<f16_t, bf16_t>), grid, blk, 0, st, n, (bf16_t*)p, (const bf16_t*)g, (f16_t*)m, (f16_t*)v, hy, cf);
-  else if (mdtype == 2 && gdtype == 1)
-    az_launch((adamw_kernel<f16_t, float>), grid, blk, 0, st, n, (bf16_t*)p, (const float*)g, (f16_t*)m, (f16_t*)v, hy, cf);
-  else
-    return AZ_ERR_ARG(60);
+  const bool ok = adamw_dispatch(mdtype, gdtype, [&](auto tm, auto tg) {
+    typedef typename decltype(tm)::type TM; typedef typename decltype(tg)::type TG;
+    if constexpr (wide) az_launch((adamw_wide_kernel<TM, TG, P>), grid, blk, 0, st, n, par, (const TG*)g, (TM*)m, (TM*)v, hy, cf, s);
+    else az_launch((adamw_kernel<TM, TG>), grid, blk, 0, st, n, par, (const TG*)g, (TM*)m, (TM*)v, hy, cf);
+  });
+  if (!ok) return AZ_ERR_ARG(60);
   AZ_CHECK_LAUNCH();
   return AZ_OK;
 }
+int launch_adamw(long n, void* p, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper, const void* coef,
+                 hipStream_t st) {
+  return launch_adamw(n, (bf16_t*)p, Split{n, 0}, g, gdtype, m, v, mdtype, hyper, coef, st);
+}
 
-// Stochastic-rounding form.  The vector body needs (elem0 + i) % 8 == 0 AND 16-byte aligned p, g, m, v at the same i: true whenever the
-// range starts on an owner's flat buffer (elem0 is then the offset in it); otherwise every element takes the scalar path.
+// Stochastic rounding: a group needs (elem0 + i) % 8 == 0 AND 16-byte aligned p, g, m, v at the same i -- true whenever the range
+// starts on an owner's flat buffer (elem0 is then the offset in it); otherwise every element takes the scalar path.
 int launch_adamw_sr(long n, void* p, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper, const void* coef,
                     long seed, long step, long domain, long elem0, hipStream_t st) {
   if (mdtype < 0 || mdtype > 2 || gdtype < 0 || gdtype > 1 || elem0 < 0) return AZ_ERR_ARG(68);
   const size_t esz = mdtype == 1 ? 4 : 2, gsz = gdtype == 0 ? 2 : 4;
-  SrArgs sr;
-  sr.k0 = (uint32_t)(unsigned long)seed; sr.k1 = (uint32_t)((unsigned long)seed >> 32);
-  sr.step = (uint32_t)step; sr.dom = (uint32_t)domain; sr.elem0 = elem0;
-  long head = (8 - (elem0 & 7)) & 7;
-  if (head > n) head = n;
-  const bool aligned = (((uintptr_t)p + head * 2) & 15) == 0 && (((uintptr_t)g + head * gsz) & 15) == 0 &&
-                       (((uintptr_t)m + head * esz) & 15) == 0 && (((uintptr_t)v + head * esz) & 15) == 0;
-  if (!aligned) head = n;
-  sr.head = head; sr.groups = (n - head) >> 3;
-  const long nscalar = n - (sr.groups << 3);
-  dim3 grid(grid_for((sr.groups > nscalar ? sr.groups : nscalar))), blk(256);
-  const float* hy = (const float*)hyper; const float* cf = (const float*)coef;
-  if (mdtype == 0 && gdtype == 0)
-    az_launch((adamw_sr_kernel<bf16_t, bf16_t>), grid, blk, 0, st, n, (bf16_t*)p, (const bf16_t*)g, (bf16_t*)m, (bf16_t*)v, hy, cf, sr);
-  else if (mdtype == 1 && gdtype == 0)
-    az_launch((adamw_sr_kernel<float, bf16_t>), grid, blk, 0, st, n, (bf16_t*)p, (const bf16_t*)g, (float*)m, (float*)v, hy, cf, sr);
-  else if (mdtype == 0 && gdtype == 1)
-    az_launch((adamw_sr_kernel<bf16_t, float>), grid, blk, 0, st, n, (bf16_t*)p, (const float*)g, (bf16_t*)m, (bf16_t*)v, hy, cf, sr);
-  else if (mdtype == 1 && gdtype == 1)
-    az_launch((adamw_sr_kernel<float, float>), grid, blk, 0, st, n, (bf16_t*)p, (const float*)g, (float*)m, (float*)v, hy, cf, sr);
-  else if (mdtype == 2 && gdtype == 0)
-    az_launch((adamw_sr_kernel<f16_t, bf16_t>), grid, blk, 0, st, n, (bf16_t*)p, (const bf16_t*)g, (f16_t*)m, (f16_t*)v, hy, cf, sr);
-  else
-    az_launch((adamw_sr_kernel<f16_t, float>), grid, blk, 0, st, n, (bf16_t*)p, (const float*)g, (f16_t*)m, (f16_t*)v, hy, cf, sr);
-  AZ_CHECK_LAUNCH();
-  return AZ_OK;
+  const SrArgs sr = {(uint32_t)(unsigned long)seed, (uint32_t)((unsigned long)seed >> 32), (uint32_t)step, (uint32_t)domain, elem0};
+  const Split s = split_for(n, {{p, 2}, {g, gsz}, {m, esz}, {v, esz}}, (8 - (elem0 & 7)) & 7);
+  return launch_adamw(n, SrParam{(bf16_t*)p, sr}, s, g, gdtype, m, v, mdtype, hyper, coef, st);
 }
 
 // ---- fp32 exponential moving average of the bf16 parameters (an option the reference does not have: INTEGRATION.md) -------------------
@@ -330,10 +360,11 @@ __device__ __forceinline__ float ema_math(float e, float p, float omd) {
 }
 
 // az_ema_flat: the scalar head [0, head), then `groups` groups of 8 elements with 16-byte accesses (one load of p, two loads and two
-// stores of e per thread), then the scalar tail up to n -- the split of adamw_sr_kernel (launch_ema computes it).
-__global__ void ema_kernel(long n, const bf16_t* __restrict__ p, float* __restrict__ e, float omd, long head, long groups) {
+// stores of e per thread), then the scalar tail up to n -- the split of adamw_wide_kernel (split_for).
+__global__ void ema_kernel(long n, const bf16_t* __restrict__ p, float* __restrict__ e, float omd, Split s) {
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long)gridDim.x * blockDim.x;
-  const long body = head + (groups << 3);                    // <= n (launch_ema)
+  const long head = s.head, groups = s.groups;
+  const long body = head + (groups << 3);                    // <= n (split_for)
   for (long gi = tid; gi < groups; gi += nthr) {
     const long i = head + (gi << 3);
     float pp[8], ee[8];
@@ -347,70 +378,6 @@ __global__ void ema_kernel(long n, const bf16_t* __restrict__ p, float* __restri
     const long i = j < head ? j : j - head + body;
     e[i] = ema_math(e[i], bf2f(p[i]), omd);
   }
-}
-
-// ---- fp32 master weights (an option the reference does not have: INTEGRATION.md "fp32 master weights") -------------------------------
-// az_adamw_flat_master: adamw_math with the fp32 master w[i] as the parameter operand; writes w[i] = pp and p[i] = bf16(pp), round to
-// nearest even -- p is never read.  The split of adamw_sr_kernel / ema_kernel: scalar head [0, head), `groups` groups of 8 elements
-// with 16-byte accesses (two loads and two stores of w per thread), scalar tail (launch_adamw_master computes it).
-template <typename TM, typename TG>
-__global__ void adamw_master_kernel(long n, bf16_t* __restrict__ p, float* __restrict__ w, const TG* __restrict__ g, TM* __restrict__ m,
-                                    TM* __restrict__ v, const float* __restrict__ hyper, const float* __restrict__ coef, long head, long groups) {
-  const AdamwK k = adamw_consts(hyper, coef);
-  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long)gridDim.x * blockDim.x;
-  const long body = head + (groups << 3);                    // <= n (launch_adamw_master)
-  for (long gi = tid; gi < groups; gi += nthr) {
-    const long i = head + (gi << 3);
-    float gg[8], mm[8], vv[8], pp[8];
-    load8<TG>(g + i, gg); load8<TM>(m + i, mm); load8<TM>(v + i, vv); load8<float>(w + i, pp);
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      adamw_math<TG>(k, [&] { return gg[e]; }, [&] { return mm[e]; }, [&] { return vv[e]; }, [&] { return pp[e]; }, mm[e], vv[e], pp[e]);
-    store8_moment<float>(w + i, pp);
-    store8_moment<bf16_t>(p + i, pp);
-    store8_moment<TM>(m + i, mm);
-    store8_moment<TM>(v + i, vv);
-  }
-  const long nscalar = n - (groups << 3);                    // head + tail
-  for (long j = tid; j < nscalar; j += nthr) {
-    const long i = j < head ? j : j - head + body;
-    float mm, vv, pp;
-    adamw_math<TG>(k, [&] { return ldf<TG>(g, i); }, [&] { return ldf<TM>(m, i); }, [&] { return ldf<TM>(v, i); }, [&] { return w[i]; },
-                   mm, vv, pp);
-    w[i] = pp;
-    p[i] = f2bf(pp);
-    stf<TM>(m, i, mm);
-    stf<TM>(v, i, vv);
-  }
-}
-
-int launch_adamw_master(long n, void* p, void* w, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper,
-                        const void* coef, hipStream_t st) {
-  const size_t esz = mdtype == 1 ? 4 : 2, gsz = gdtype == 0 ? 2 : 4;
-  // first element where p, g, m, v AND w are 16-byte aligned, h in [0, 8); none (the five pointers cannot be co-aligned) or beyond
-  // the range: every element takes the scalar form
-  long head = n;
-  for (long h = 0; h < 8; ++h)
-    if ((((uintptr_t)p + 2 * h) & 15) == 0 && (((uintptr_t)w + 4 * h) & 15) == 0 && (((uintptr_t)g + gsz * h) & 15) == 0 &&
-        (((uintptr_t)m + esz * h) & 15) == 0 && (((uintptr_t)v + esz * h) & 15) == 0) { head = h < n ? h : n; break; }
-  const long groups = (n - head) >> 3, nscalar = n - (groups << 3);
-  dim3 grid(grid_for(groups > nscalar ? groups : nscalar)), blk(256);
-  const float* hy = (const float*)hyper; const float* cf = (const float*)coef;
-  bf16_t* pb = (bf16_t*)p; float* wf = (float*)w;
-  if (mdtype == 0 && gdtype == 0)
-    az_launch((adamw_master_kernel<bf16_t, bf16_t>), grid, blk, 0, st, n, pb, wf, (const bf16_t*)g, (bf16_t*)m, (bf16_t*)v, hy, cf, head, groups);
-  else if (mdtype == 1 && gdtype == 0)
-    az_launch((adamw_master_kernel<float, bf16_t>), grid, blk, 0, st, n, pb, wf, (const bf16_t*)g, (float*)m, (float*)v, hy, cf, head, groups);
-  else if (mdtype == 0 && gdtype == 1)
-    az_launch((adamw_master_kernel<bf16_t, float>), grid, blk, 0, st, n, pb, wf, (const float*)g, (bf16_t*)m, (bf16_t*)v, hy, cf, head, groups);
-  else if (mdtype == 1 && gdtype == 1)
-    az_launch((adamw_master_kernel<float, float>), grid, blk, 0, st, n, pb, wf, (const float*)g, (float*)m, (float*)v, hy, cf, head, groups);
-  else if (mdtype == 2 && gdtype == 0)
-    az_launch((adamw_master_kernel<f16_t, bf16_t>), grid, blk, 0, st, n, pb, wf, (const bf16_t*)g, (f16_t*)m, (f16_t*)v, hy, cf, head, groups);
-  else
-    az_launch((adamw_master_kernel<f16_t, float>), grid, blk, 0, st, n, pb, wf, (const float*)g, (f16_t*)m, (f16_t*)v, hy, cf, head, groups);
-  AZ_CHECK_LAUNCH();
-  return AZ_OK;
 }
 
 // Hand-off events of the chunk pipeline, one set per COMPUTE STREAM (a stream belongs to one device, so two optimizers,
@@ -537,14 +504,8 @@ int az_adamw_flat_sr(long n, void* p, const void* g, int gdtype, void* m, void* 
 int az_ema_flat(long n, const void* p, void* ema_f32, float one_minus_decay, void* stream) {
   if (n < 0 || !p || !ema_f32 || ((uintptr_t)p & 1) || ((uintptr_t)ema_f32 & 3)) return AZ_ERR_ARG(69);
   if (n == 0) return AZ_OK;
-  // first element where p AND e are 16-byte aligned: p + 2 h and e + 4 h, h in [0, 8); none (the two pointers cannot be co-aligned) or
-  // beyond the range: every element takes the scalar form
-  long head = n;
-  for (long h = 0; h < 8; ++h)
-    if ((((uintptr_t)p + 2 * h) & 15) == 0 && (((uintptr_t)ema_f32 + 4 * h) & 15) == 0) { head = h < n ? h : n; break; }
-  const long groups = (n - head) >> 3, nscalar = n - (groups << 3);
-  az_launch(ema_kernel, dim3(grid_for(groups > nscalar ? groups : nscalar)), dim3(256), 0, (hipStream_t)stream, n, (const bf16_t*)p,
-            (float*)ema_f32, one_minus_decay, head, groups);
+  const Split s = split_for(n, {{p, 2}, {ema_f32, 4}});
+  az_launch(ema_kernel, dim3(grid_for(n, s)), dim3(256), 0, (hipStream_t)stream, n, (const bf16_t*)p, (float*)ema_f32, one_minus_decay, s);
   AZ_CHECK_LAUNCH();
   return AZ_OK;
 }
@@ -556,7 +517,8 @@ int az_adamw_flat_master(long n, void* p, void* w_f32, const void* g, int gdtype
   if (((uintptr_t)p & 1) || ((uintptr_t)w_f32 & 3) || ((uintptr_t)g & gmask) || ((uintptr_t)m & emask) || ((uintptr_t)v & emask))
     return AZ_ERR_ARG(77);
   if (n == 0) return AZ_OK;
-  return launch_adamw_master(n, p, w_f32, g, gdtype, m, v, mdtype, hyper, coef, (hipStream_t)stream);
+  const Split s = split_for(n, {{p, 2}, {w_f32, 4}, {g, gmask + 1}, {m, emask + 1}, {v, emask + 1}});
+  return launch_adamw(n, MasterParam{(bf16_t*)p, (float*)w_f32}, s, g, gdtype, m, v, mdtype, hyper, coef, (hipStream_t)stream);
 }
 
 int az_raven_step_ex(long n, void* p, const void* g, int gdtype, void* m_host, void* v_host, int mdtype, const void* hyper,

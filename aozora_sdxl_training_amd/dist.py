@@ -37,7 +37,6 @@ import torch
 from . import ops
 from ._lib import lib
 
-_MD = {torch.bfloat16: 0, torch.float32: 1, torch.float16: 2}
 MASTER_SR_REFUSAL = ("master_weights and stochastic_rounding do not combine: stochastic rounding exists because there is no fp32 master "
                      "copy -- with one, the bf16 parameters are its round-to-nearest image; choose one of the two")
 
@@ -383,13 +382,72 @@ class ShardedRaven:
         for side in u._sides:                  # parameter-gradient branch stream(s)
             ev = torch.cuda.Event(); ev.record(side); self.comm.wait_event(ev)
         with torch.cuda.stream(self.comm):
+            self._before_tail_reduce(k)
             self._reduce_region(k)
         self._reduced.add(k)
+
+    def _before_tail_reduce(self, k):
+        """On the communication stream, in front of region k's reduce-scatter in reduce_tail (ShardedTitan: into the accumulator)."""
+
+    def _grad(self):
+        """The gradients the norm and the update read: (flat buffer, element size, gdtype of ops.adamw_range)."""
+        return self.unet.gflat, 2, 0
+
+    def _reduce_and_clip(self, main):
+        """The middle of step(): reduce the regions (in place: rank r's reduced shard of region i lands in own[i]; regions that
+        reduce_tail sent ahead are on their way, the rest follows on the same stream), global norm over the owned trainable ranges
+        (+ scalar all-reduce) -> clip coefficient in scal[1]; `main` then waits for the m / v prefetch."""
+        if self.exchange:
+            if self.overlap:
+                self.comm.wait_stream(main)
+                with torch.cuda.stream(self.comm):
+                    for i in (2, 1, 0):
+                        if i not in self._reduced:
+                            self._reduce_region(i)
+                main.wait_stream(self.comm)
+            else:
+                for i in range(len(self.regions)):
+                    self._reduce_region(i)
+        self._reduced = set()
+        gbuf = self._grad()[0]
+        first = True
+        for rs in self.ranges:
+            for a, b in rs:
+                ops.sumsq(gbuf[a:b], self.scal[0:1], not first)
+                first = False
+        if first:
+            self.scal[0:1].zero_()
+        if self.exchange:
+            self.dist.all_reduce(self.scal[0:1], op=self.dist.ReduceOp.SUM, group=self.pg)
+        mx = float(self.clip) if self.clip and self.clip > 0 else float("inf")
+        ops.clip_coef(self.scal[0:1], mx, self.scal[1:2], self.scal[2:3])
+        if self._h2d_done is not None:
+            main.wait_event(self._h2d_done)
+
+    def _update_region(self, i, stream):
+        """AdamW over the owned trainable ranges of region i on `stream`, the clip coefficient applied in-kernel."""
+        u = self.unet
+        gbuf, gsz, gdtype = self._grad()
+        esz = self.m_dev.element_size()
+        for (a, b), hoff in zip(self.ranges[i], self.range_off[i]):
+            ops.adamw_range(b - a, u.pflat.data_ptr() + a * 2, gbuf.data_ptr() + a * gsz, gdtype, self.m_dev.data_ptr() + hoff * esz,
+                            self.v_dev.data_ptr() + hoff * esz, self.mdt, self.hyper_dev.data_ptr(), self.scal[1:2].data_ptr(), stream.cuda_stream,
+                            master=self.w_dev.data_ptr() + hoff * 4 if self.master else None,
+                            sr=(self.sr_seed, self.step_count, 0, a) if self.sr else None)
+
+    def _gather_regions(self, regions):
+        """On the communication stream (current), per region: all-gather, then its W^T copies, then an event -> [(region, event)]."""
+        out = []
+        for i in regions:
+            self._gather_region(i)
+            self.unet._refresh_jobs(*self.regions[i])
+            ev = torch.cuda.Event(); ev.record(self.comm)
+            out.append((i, ev))
+        return out
 
     def step(self) -> torch.Tensor:
         """reduce -> clip -> update owned shards -> gather.  Returns the pre-clip global grad norm (0-d device tensor)."""
         u = self.unet
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         main = torch.cuda.current_stream()
         boundary = self._span("optimizer_boundary_on_main_stream", main)
         boundary.__enter__()
@@ -402,60 +460,13 @@ class ShardedRaven:
         u.wait_tail_params()
         self._hyper()
         self.prefetch()
-        if self.exchange:          # in place: rank r's reduced shard of region i lands in gflat[own[i]]
-            if self.overlap:
-                self.comm.wait_stream(main)
-                with torch.cuda.stream(self.comm):
-                    for i in (2, 1, 0):
-                        if i not in self._reduced:
-                            self._reduce_region(i)
-                main.wait_stream(self.comm)
-            else:
-                for i in range(len(self.regions)):
-                    self._reduce_region(i)
-        self._reduced = set()
-        # grad norm over owned trainable ranges (+ scalar all-reduce)
-        first = True
-        for rs in self.ranges:
-            for a, b in rs:
-                ops.sumsq(u.gflat[a:b], self.scal[0:1], not first)
-                first = False
-        if first:
-            self.scal[0:1].zero_()
-        if self.exchange:
-            self.dist.all_reduce(self.scal[0:1], op=self.dist.ReduceOp.SUM, group=self.pg)
-        mx = float(self.clip) if self.clip and self.clip > 0 else float("inf")
-        ops.clip_coef(self.scal[0:1], mx, self.scal[1:2], self.scal[2:3])
-        esz = 4 if self.mdt == torch.float32 else 2
-        L = lib()
-        if self._h2d_done is not None:
-            main.wait_event(self._h2d_done)
-
-        def update_region(i, stream):
-            sp = ctypes.c_void_p(stream.cuda_stream)
-            for k, (a, b) in enumerate(self.ranges[i]):
-                hoff = self.range_off[i][k]
-                if self.master:
-                    L.call("az_adamw_flat_master", b - a, ctypes.c_void_p(u.pflat.data_ptr() + a * 2), ctypes.c_void_p(self.w_dev.data_ptr() + hoff * 4),
-                           ctypes.c_void_p(u.gflat.data_ptr() + a * 2), 0,
-                           ctypes.c_void_p(self.m_dev.data_ptr() + hoff * esz), ctypes.c_void_p(self.v_dev.data_ptr() + hoff * esz),
-                           _MD[self.mdt], ctypes.c_void_p(self.hyper_dev.data_ptr()), ctypes.c_void_p(self.scal[1:2].data_ptr()), sp)
-                    continue
-                if self.sr:
-                    L.call("az_adamw_flat_sr", b - a, ctypes.c_void_p(u.pflat.data_ptr() + a * 2), ctypes.c_void_p(u.gflat.data_ptr() + a * 2), 0,
-                           ctypes.c_void_p(self.m_dev.data_ptr() + hoff * esz), ctypes.c_void_p(self.v_dev.data_ptr() + hoff * esz),
-                           _MD[self.mdt], ctypes.c_void_p(self.hyper_dev.data_ptr()), ctypes.c_void_p(self.scal[1:2].data_ptr()),
-                           self.sr_seed, self.step_count, 0, a, sp)
-                    continue
-                L.call("az_adamw_flat", b - a, ctypes.c_void_p(u.pflat.data_ptr() + a * 2), ctypes.c_void_p(u.gflat.data_ptr() + a * 2),
-                       ctypes.c_void_p(self.m_dev.data_ptr() + hoff * esz), ctypes.c_void_p(self.v_dev.data_ptr() + hoff * esz),
-                       _MD[self.mdt], ctypes.c_void_p(self.hyper_dev.data_ptr()), ctypes.c_void_p(self.scal[1:2].data_ptr()), sp)   # clip coefficient applied in-kernel
+        self._reduce_and_clip(main)
         if self.update_overlap:
             # on the parameter-gradient stream: idle during a forward, and the one stream known to run well beside the main one
             # (a first use of the communication stream re-deals the hardware queues: the m / v copy streams then shared one with
             # the compute streams and the window's last micro-steps ran 124 / 161 ms instead of 117 -- measured, streams.py)
             bg = self._bg = u._sides[0]
-            update_region(0, main)                     # what the forward reads first stays on the main stream (3 % of the elements)
+            self._update_region(0, main)               # what the forward reads first stays on the main stream (3 % of the elements)
             # region 0's EMA goes IN FRONT of the hand-over: the background updates then start 0.13 ms later (SDXL-base), which the forward
             # never sees -- behind the hand-over it shares the device with region 1's update and held the main stream 0.88 ms instead
             # (tools/ema_time.py, INTEGRATION.md "EMA of the weights")
@@ -465,7 +476,7 @@ class ShardedRaven:
                 later = []
                 for i in (1, 2):
                     with self._span(f"update_region{i}", bg, (20 if self.master else 14) * sum(b - a for a, b in self.ranges[i])):
-                        update_region(i, bg)
+                        self._update_region(i, bg)
                     ev = torch.cuda.Event(); ev.record(bg)
                     later.append((i, ev))
                 upd = torch.cuda.Event(); upd.record(bg)
@@ -486,23 +497,16 @@ class ShardedRaven:
             # data parallel, overlapped: only region 0's shard is updated on the main stream; the shards of regions 1 / 2 are updated on the
             # exchange stream in front of their all-gathers, under the next forward (which waits per region where it first reads) -- the
             # one-rank schedule above with the all-gathers added.  Rehearsed at pretend N = 8: boundary 1.74 -> 0.6 ms per iteration.
-            update_region(0, main)
+            self._update_region(0, main)
             upd0 = torch.cuda.Event(); upd0.record(main)       # (also orders the clip coefficient, the hyper-parameters and the m / v staging)
             self.comm.wait_event(upd0)
             self._ema_regions((0,), main)              # reads this rank's own shard only: runs beside all-gather(0), which does not write it
             with torch.cuda.stream(self.comm):
-                self._gather_region(0)
-                u._refresh_jobs(*self.regions[0])
-                head = torch.cuda.Event(); head.record(self.comm)
+                head = self._gather_regions((0,))[0][1]
                 for i in (1, 2):
-                    update_region(i, self.comm)
+                    self._update_region(i, self.comm)
                 upd = torch.cuda.Event(); upd.record(self.comm)
-                later = []
-                for i in (1, 2):
-                    self._gather_region(i)
-                    u._refresh_jobs(*self.regions[i])
-                    ev = torch.cuda.Event(); ev.record(self.comm)
-                    later.append((i, ev))
+                later = self._gather_regions((1, 2))
                 self._ema_regions((1, 2), self.comm)   # behind the gathers and their events, ahead of the next step's updates on this stream
             main.wait_event(head)
             for i, ev in later:
@@ -515,7 +519,7 @@ class ShardedRaven:
             self._boundary.__exit__()
             return self.scal[2]
         for i in range(len(self.ranges)):
-            update_region(i, main)
+            self._update_region(i, main)
         self._finish_step(main)
         self._boundary.__exit__()
         return self.scal[2]
@@ -546,15 +550,8 @@ class ShardedRaven:
             if self.overlap:
                 self.comm.wait_event(upd)
                 with torch.cuda.stream(self.comm):   # each region: all-gather, then its W^T copies, also on this stream
-                    self._gather_region(0)
-                    u._refresh_jobs(*self.regions[0])
-                    head = torch.cuda.Event(); head.record(self.comm)
-                    later = []
-                    for i in (1, 2):                 # land under the next forward (before the last down block / the mid block)
-                        self._gather_region(i)
-                        u._refresh_jobs(*self.regions[i])
-                        ev = torch.cuda.Event(); ev.record(self.comm)
-                        later.append((i, ev))
+                    head = self._gather_regions((0,))[0][1]
+                    later = self._gather_regions((1, 2))     # land under the next forward (before the last down block / the mid block)
                 self._ema_regions(range(len(self.ranges)), main)      # beside the gathers (they read, and leave alone, the owned shards)
                 main.wait_event(head)
                 for i, ev in later:
@@ -749,24 +746,16 @@ class ShardedTitan(ShardedRaven):
                 self._accumulate_ranges(rs, main)
         self._acc_started = True
 
-    def reduce_tail(self, k=2):
-        """Hook for the LAST micro-step of the window (TrainStep.micro_step(after_tail=...)), as ShardedRaven.reduce_tail: when the
-        backward has issued every gradient of region k, that region's bf16 gradients join the fp32 accumulator and its fp32
-        reduce-scatter starts -- both on the communication stream, under the rest of the backward.  This is where the
-        reference's post-accumulate hooks move each gradient DURING the backward (titan.py:93-100, 119-131); without it the
-        whole 10.3 GB exchange of cfg5 sat behind the last backward.  Arithmetic unchanged: the same fp32 additions in the
-        same order (tests/test_dp_gpu.py: bitwise equal to the serial form)."""
-        if not self.overlap or k in self._reduced:
-            return
-        u = self.unet
-        main = torch.cuda.current_stream()
-        ev = torch.cuda.Event(); ev.record(main); self.comm.wait_event(ev)
-        for side in u._sides:                  # parameter-gradient branch stream(s)
-            ev = torch.cuda.Event(); ev.record(side); self.comm.wait_event(ev)
-        with torch.cuda.stream(self.comm):
-            self._accumulate_ranges(self._region_trainable[k], self.comm)
-            self._reduce_region(k)
-        self._reduced.add(k)
+    def _before_tail_reduce(self, k):
+        """ShardedRaven.reduce_tail for Titan: when the backward has issued every gradient of region k, that region's bf16 gradients
+        join the fp32 accumulator and its fp32 reduce-scatter starts -- both on the communication stream, under the rest of the
+        backward.  This is where the reference's post-accumulate hooks move each gradient DURING the backward (titan.py:93-100,
+        119-131); without it the whole 10.3 GB exchange of cfg5 sat behind the last backward.  Arithmetic unchanged: the same fp32
+        additions in the same order (tests/test_dp_gpu.py: bitwise equal to the serial form)."""
+        self._accumulate_ranges(self._region_trainable[k], self.comm)
+
+    def _grad(self):
+        return self.gacc, 4, 1
 
     def _reduce_region(self, i):
         a, b = self.regions[i]
@@ -780,8 +769,6 @@ class ShardedTitan(ShardedRaven):
         return None
 
     def step(self) -> torch.Tensor:
-        u = self.unet
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         main = torch.cuda.current_stream()
         if not self._acc_started:
             raise RuntimeError("ShardedTitan.step() without accumulate(): no gradients in the fp32 accumulator")
@@ -790,52 +777,10 @@ class ShardedTitan(ShardedRaven):
             self.ema.begin_update()
         self._hyper()
         self.prefetch()
-        u.wait_tail_params()
-        if self.exchange:
-            if self.overlap:           # regions 2 / 1 may already be on their way (reduce_tail); the rest follows on the same stream
-                self.comm.wait_stream(main)
-                with torch.cuda.stream(self.comm):
-                    for i in (2, 1, 0):
-                        if i not in self._reduced:
-                            self._reduce_region(i)
-                main.wait_stream(self.comm)
-            else:
-                for i in range(len(self.regions)):
-                    self._reduce_region(i)
-        self._reduced = set()
-        first = True
-        for rs in self.ranges:
-            for a, b in rs:
-                ops.sumsq(self.gacc[a:b], self.scal[0:1], not first)
-                first = False
-        if first:
-            self.scal[0:1].zero_()
-        if self.exchange:
-            self.dist.all_reduce(self.scal[0:1], op=self.dist.ReduceOp.SUM, group=self.pg)
-        mx = float(self.clip) if self.clip and self.clip > 0 else float("inf")
-        ops.clip_coef(self.scal[0:1], mx, self.scal[1:2], self.scal[2:3])
-        esz = 4 if self.mdt == torch.float32 else 2
-        L = lib()
-        if self._h2d_done is not None:
-            main.wait_event(self._h2d_done)
-        for i, rs in enumerate(self.ranges):
-            for k, (a, b) in enumerate(rs):
-                hoff = self.range_off[i][k]
-                if self.master:
-                    L.call("az_adamw_flat_master", b - a, ctypes.c_void_p(u.pflat.data_ptr() + a * 2), ctypes.c_void_p(self.w_dev.data_ptr() + hoff * 4),
-                           ctypes.c_void_p(self.gacc.data_ptr() + a * 4), 1,
-                           ctypes.c_void_p(self.m_dev.data_ptr() + hoff * esz), ctypes.c_void_p(self.v_dev.data_ptr() + hoff * esz),
-                           _MD[self.mdt], ctypes.c_void_p(self.hyper_dev.data_ptr()), ctypes.c_void_p(self.scal[1:2].data_ptr()), st)
-                    continue
-                if self.sr:
-                    L.call("az_adamw_flat_sr", b - a, ctypes.c_void_p(u.pflat.data_ptr() + a * 2), ctypes.c_void_p(self.gacc.data_ptr() + a * 4), 1,
-                           ctypes.c_void_p(self.m_dev.data_ptr() + hoff * esz), ctypes.c_void_p(self.v_dev.data_ptr() + hoff * esz),
-                           _MD[self.mdt], ctypes.c_void_p(self.hyper_dev.data_ptr()), ctypes.c_void_p(self.scal[1:2].data_ptr()),
-                           self.sr_seed, self.step_count, 0, a, st)
-                    continue
-                L.call("az_adamw_flat_ex", b - a, ctypes.c_void_p(u.pflat.data_ptr() + a * 2), ctypes.c_void_p(self.gacc.data_ptr() + a * 4), 1,
-                       ctypes.c_void_p(self.m_dev.data_ptr() + hoff * esz), ctypes.c_void_p(self.v_dev.data_ptr() + hoff * esz),
-                       _MD[self.mdt], ctypes.c_void_p(self.hyper_dev.data_ptr()), ctypes.c_void_p(self.scal[1:2].data_ptr()), st)
+        self.unet.wait_tail_params()
+        self._reduce_and_clip(main)
+        for i in range(len(self.ranges)):
+            self._update_region(i, main)
         self._acc_started = False
         self._finish_step(main)
         return self.scal[2]

@@ -685,7 +685,32 @@ def ema_flat(p, ema, one_minus_decay, stream=None):
     lib().call("az_ema_flat", p.numel(), _ptr(p), _ptr(ema), float(one_minus_decay), st)
 
 
-_MOMENT_CODE = {BF16: 0, F32: 1, torch.float16: 2}
+MOMENT_CODE = {BF16: 0, F32: 1, torch.float16: 2}      # mdtype of the C ABI
+
+
+def adamw_range(n, p, g, gdtype, m, v, mdtype, hyper, coef, stream, *, master=None, sr=None, host_pipeline=None):
+    """The Raven / Titan AdamW update of ONE flat range of n elements -- the one place that names the az_adamw_flat* / az_raven_step*
+    entry points.  Everything is a raw address or handle (optimizers.RavenAdamW works on storage spans, not tensors), checked by the
+    caller: p bf16 parameters, g gradients (gdtype 0 bf16, 1 fp32), m / v moments of torch dtype `mdtype`, hyper the fp32 vector of
+    az_adamw_flat, coef the fp32 clip coefficient (None / 0: none), stream the compute stream.
+      master=address           fp32 master copy, read and written; p receives bf16(master) (az_adamw_flat_master)
+      sr=(seed, step, domain, elem0)                                   stochastic rounding of the bf16 write (az_adamw_flat_sr)
+      host_pipeline=(staging address, chunk_elems, h2d stream, d2h stream)    m / v are PINNED HOST memory, streamed in chunks through
+                               the device staging buffer on the two copy streams (az_raven_step_ex / az_raven_step_sr)
+    master combines with neither of the other two: no entry point."""
+    if master is not None and (sr is not None or host_pipeline is not None):
+        raise AozoraError("adamw_range: master weights combine with neither stochastic rounding nor the pinned-host pipeline")
+    vp = ctypes.c_void_p
+    rest = (vp(g), int(gdtype), vp(m), vp(v), MOMENT_CODE[mdtype], vp(hyper), vp(coef or 0))
+    sr = tuple(int(x) for x in sr) if sr is not None else ()
+    if master is not None:
+        lib().call("az_adamw_flat_master", int(n), vp(p), vp(master), *rest, vp(stream))
+    elif host_pipeline is None:
+        lib().call("az_adamw_flat_sr" if sr else "az_adamw_flat_ex", int(n), vp(p), *rest, *sr, vp(stream))
+    else:
+        staging, chunk_elems, h2d, d2h = host_pipeline
+        lib().call("az_raven_step_sr" if sr else "az_raven_step_ex", int(n), vp(p), *rest, vp(staging), int(chunk_elems), vp(stream), vp(h2d),
+                   vp(d2h), *sr)
 
 
 def adamw_flat_master(p, w, g, m, v, hyper, coef=None, stream=None):
@@ -695,13 +720,13 @@ def adamw_flat_master(p, w, g, m, v, hyper, coef=None, stream=None):
     ts = (p, w, g, m, v)
     _req(all(t.is_cuda and t.device == p.device for t in ts + (hyper,)) and (coef is None or (coef.is_cuda and coef.device == p.device)),
          "adamw_flat_master needs cuda tensors on one device")
-    _req(p.dtype == BF16 and w.dtype == F32 and g.dtype in (BF16, F32) and m.dtype in _MOMENT_CODE and v.dtype == m.dtype,
+    _req(p.dtype == BF16 and w.dtype == F32 and g.dtype in (BF16, F32) and m.dtype in MOMENT_CODE and v.dtype == m.dtype,
          "adamw_flat_master needs bf16 p, fp32 w, bf16 / fp32 g and bf16 / fp32 / fp16 moments of one type")
     _req(all(t.dim() == 1 and t.is_contiguous() and t.numel() == p.numel() for t in ts), "adamw_flat_master shapes")
     _req(hyper.dtype == F32 and hyper.is_contiguous() and hyper.numel() >= 7, "adamw_flat_master needs the fp32 hyper vector of 7+ entries")
     _req(coef is None or (coef.dtype == F32 and coef.numel() >= 1), "adamw_flat_master needs an fp32 clip coefficient")
     if p.numel() == 0:             # (an empty tensor has no address to hand over)
         return
-    st = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
-    lib().call("az_adamw_flat_master", p.numel(), _ptr(p), _ptr(w), _ptr(g), int(g.dtype == F32), _ptr(m), _ptr(v), _MOMENT_CODE[m.dtype],
-               _ptr(hyper), _ptr(coef), st)
+    adamw_range(p.numel(), p.data_ptr(), g.data_ptr(), int(g.dtype == F32), m.data_ptr(), v.data_ptr(), m.dtype, hyper.data_ptr(),
+                coef.data_ptr() if coef is not None else None, (stream if stream is not None else torch.cuda.current_stream()).cuda_stream,
+                master=w.data_ptr())

@@ -13,16 +13,15 @@ surface and the same element arithmetic (fp32 math, `debias_strength`, m/v store
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from typing import Dict, List
 
 import torch
 from torch.optim import Optimizer
 
-from .._lib import lib, AozoraError
+from .. import ops
+from .._lib import AozoraError
 
-_MD = {torch.bfloat16: 0, torch.float32: 1, torch.float16: 2}
 CHUNK_ELEMS = 16 << 20
 
 
@@ -223,37 +222,15 @@ class RavenAdamW(Optimizer):
         self._hyper_ev = torch.cuda.Event()
         self._hyper_ev.record(sc)
         esz = 4 if self._momentum_dtype == torch.float32 else 2
-        coef = self.clip_coef if self.clip_coef is not None else None
-        L = lib()
+        coef = self.clip_coef.data_ptr() if self.clip_coef is not None else None
+        # resident moments: the update kernel alone, on the compute stream; pinned host moments: the chunk pipeline on three streams
+        pipe = None if self._state_on_device else (self._staging.data_ptr(), CHUNK_ELEMS, self._copy_streams[0].cuda_stream,
+                                                   self._copy_streams[1].cuda_stream)
         for i, (pptr, gptr, key, hoff, n, _, srk) in enumerate(segs):
             hs = self._host[key]
-            if srk is not None:               # the same two calls with the bf16 write-back stochastically rounded
-                sr = (self._sr_seed, srk[0], srk[1], hoff)
-                if self._state_on_device:
-                    L.call("az_adamw_flat_sr", n, ctypes.c_void_p(pptr), ctypes.c_void_p(gptr), self._GDTYPE,
-                           ctypes.c_void_p(hs.m.data_ptr() + hoff * esz), ctypes.c_void_p(hs.v.data_ptr() + hoff * esz),
-                           _MD[self._momentum_dtype], ctypes.c_void_p(self._hyper_dev[i].data_ptr()),
-                           ctypes.c_void_p(coef.data_ptr() if coef is not None else 0), *sr, ctypes.c_void_p(sc.cuda_stream))
-                    continue
-                L.call("az_raven_step_sr", n, ctypes.c_void_p(pptr), ctypes.c_void_p(gptr), self._GDTYPE,
-                       ctypes.c_void_p(hs.m.data_ptr() + hoff * esz), ctypes.c_void_p(hs.v.data_ptr() + hoff * esz),
-                       _MD[self._momentum_dtype], ctypes.c_void_p(self._hyper_dev[i].data_ptr()),
-                       ctypes.c_void_p(coef.data_ptr() if coef is not None else 0), ctypes.c_void_p(self._staging.data_ptr()),
-                       CHUNK_ELEMS, ctypes.c_void_p(sc.cuda_stream), ctypes.c_void_p(self._copy_streams[0].cuda_stream),
-                       ctypes.c_void_p(self._copy_streams[1].cuda_stream), *sr)
-                continue
-            if self._state_on_device:          # resident moments: the update kernel alone, on the compute stream
-                L.call("az_adamw_flat_ex", n, ctypes.c_void_p(pptr), ctypes.c_void_p(gptr), self._GDTYPE,
-                       ctypes.c_void_p(hs.m.data_ptr() + hoff * esz), ctypes.c_void_p(hs.v.data_ptr() + hoff * esz),
-                       _MD[self._momentum_dtype], ctypes.c_void_p(self._hyper_dev[i].data_ptr()),
-                       ctypes.c_void_p(coef.data_ptr() if coef is not None else 0), ctypes.c_void_p(sc.cuda_stream))
-                continue
-            L.call("az_raven_step_ex", n, ctypes.c_void_p(pptr), ctypes.c_void_p(gptr), self._GDTYPE,
-                   ctypes.c_void_p(hs.m.data_ptr() + hoff * esz), ctypes.c_void_p(hs.v.data_ptr() + hoff * esz),
-                   _MD[self._momentum_dtype], ctypes.c_void_p(self._hyper_dev[i].data_ptr()),
-                   ctypes.c_void_p(coef.data_ptr() if coef is not None else 0), ctypes.c_void_p(self._staging.data_ptr()),
-                   CHUNK_ELEMS, ctypes.c_void_p(sc.cuda_stream), ctypes.c_void_p(self._copy_streams[0].cuda_stream),
-                   ctypes.c_void_p(self._copy_streams[1].cuda_stream))
+            ops.adamw_range(n, pptr, gptr, self._GDTYPE, hs.m.data_ptr() + hoff * esz, hs.v.data_ptr() + hoff * esz, self._momentum_dtype,
+                            self._hyper_dev[i].data_ptr(), coef, sc.cuda_stream, host_pipeline=pipe,
+                            sr=(self._sr_seed, srk[0], srk[1], hoff) if srk is not None else None)
         self.clip_coef = None
         for key in self._host:
             if hasattr(key, "mark_params_dirty"):
