@@ -47,7 +47,7 @@ def rnd(*shape, scale=1.0, seed=None):
 
 @pytest.fixture(params=[(0, 0, 0), (256, 256, 0), (128, 160, 8), (128, 160, 24), (128, 128, 8),
                         (128, 160, 40), (128, 160, 56), (256, 256, 32),      # 40 / 56 / 32: rings of 4 / 5 / 4 stages of 32-deep k-tiles
-                        (256, 256, 8), (256, 320, 8)],                        # the 8-wave ping-pong tile (az_gemm8.inc), 256 / 320 wide
+                        (256, 256, 8), (256, 320, 8), (128, 160, 72)],        # the 8-wave ping-pong tile (az_gemm8.inc), 256 / 320 wide; 72: 4 stages of 64-deep k-tiles
                 ids=lambda t: f"tile{t[0]}x{t[1]}w{t[2]}")
 def tile(request, ops):
     """GEMM / conv tests run under the heuristic and under every forced cooperative tile (the 128x160 tile exists for
