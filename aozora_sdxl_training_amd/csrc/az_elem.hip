@@ -415,6 +415,75 @@ __global__ void mse_finalize_kernel(int B, int C, int HW, int nblk, const float*
   }
 }
 
+// ---- robust losses (LOSS_TYPE: l1 / huber / smooth_l1; not in the reference) ----------------------------------------------------
+// l(x) and l'(x) of one residual.  KIND 1: |x|, sign(x) (+0 at 0).  KIND 2 / 3: the pseudo-Huber 2c(sqrt(x^2+c^2) - c) and
+// 2(sqrt(x^2+c^2) - c) in their cancellation-free spelling  c2 x^2 / (sqrt(x^2+c^2) + c),  c2 x / sqrt(x^2+c^2)  with c2 = 2c or 2:
+// the difference form loses every bit once |x| << c (it is exactly 0 at c = 2^20, |x| ~ 1).  cc = c * c.  sqrtf and / are correctly
+// rounded (no fast-math); contraction is off so that tests/loss_ref.py restates the operations one by one.
+template <int KIND>
+__device__ __forceinline__ void robust_elem(float x, float c, float cc, float c2, float& l, float& dl) {
+#pragma clang fp contract(off)
+  if (KIND == 1) {
+    l = fabsf(x);
+    dl = x > 0.f ? 1.f : (x < 0.f ? -1.f : (x == 0.f ? 0.f : x));      // a NaN stays a NaN
+  } else {
+    float t = x * x;
+    float r = sqrtf(t + cc);
+    l = (c2 * t) / (r + c);
+    dl = (c2 * x) / r;
+  }
+}
+// one thread per (b, pixel), as mse_kernel: C channel planes of the target (coalesced along pixels), one NHWC row of pred read and
+// one of dpred written -- as ONE 8-byte load and ONE 8- or 16-byte store when C = 4 and the rows are aligned (pvec / dvec; the
+// latent shapes of the step), element by element otherwise.  Partial sums as mse_kernel: partial[b][block], summed in block order
+// by mse_finalize_kernel (no atomics).
+template <int KIND>
+__global__ __launch_bounds__(256) void robust_loss_kernel(int B, int C, int HW, const bf16_t* __restrict__ pred, long ldp,
+                                                          const float* __restrict__ target, const float* __restrict__ w,
+                                                          const float* __restrict__ cw, float gscale, float* partial,
+                                                          bf16_t* __restrict__ dpred, int cpad, int pvec, int dvec) {
+  __shared__ float sh[16];
+  const int b = blockIdx.y;
+  const float k = gscale * w[b] / ((float)C * (float)HW * (float)B);
+  const float c = KIND == 1 ? 0.f : cw[b];
+  const float cc = c * c, c2 = KIND == 2 ? 2.0f * c : 2.0f;
+  float acc = 0.f;
+  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += (long)gridDim.x * blockDim.x) {
+    const long row = (long)b * HW + p;
+    const float* tg = target + (long)b * C * HW + p;
+    if (pvec) {                                  // C == 4
+      const uint2 u = *reinterpret_cast<const uint2*>(pred + row * ldp);
+      const float pr[4] = {__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u), __uint_as_float(u.y << 16),
+                           __uint_as_float(u.y & 0xFFFF0000u)};
+      float g[4];
+#pragma unroll
+      for (int ch = 0; ch < 4; ++ch) {
+        float l, dl;
+        robust_elem<KIND>(pr[ch] - tg[(long)ch * HW], c, cc, c2, l, dl);
+        acc += l;
+        g[ch] = k * dl;
+      }
+      if (dvec == 8) *reinterpret_cast<uint4*>(dpred + row * 8) = make_uint4(pack2bf(g[0], g[1]), pack2bf(g[2], g[3]), 0u, 0u);
+      else if (dvec == 4) *reinterpret_cast<uint2*>(dpred + row * 4) = make_uint2(pack2bf(g[0], g[1]), pack2bf(g[2], g[3]));
+      else if (dpred)
+        for (int ch = 0; ch < cpad; ++ch) dpred[row * cpad + ch] = ch < 4 ? f2bf(g[ch]) : (bf16_t)0;
+    } else {
+      for (int ch = 0; ch < cpad; ++ch) {
+        bf16_t g = 0;
+        if (ch < C) {
+          float l, dl;
+          robust_elem<KIND>(bf2f(pred[row * ldp + ch]) - tg[(long)ch * HW], c, cc, c2, l, dl);
+          acc += l;
+          g = f2bf(k * dl);
+        }
+        if (dpred) dpred[row * cpad + ch] = g;
+      }
+    }
+  }
+  float tot = block_sum(acc, sh);
+  if (threadIdx.x == 0) partial[(long)b * gridDim.x + blockIdx.x] = tot;
+}
+
 }  // namespace
 
 // ---- per-micro-step input staging: up to 8 device-to-device segments (4-byte words) and up to 256 host floats, ONE launch -------
@@ -649,6 +718,25 @@ int az_mse_loss_fwd_bwd(int batch, int C, int HW, const void* pred, long ldp, co
   int gx = (HW + 255) / 256; if (gx > 64) gx = 64;          // scratch: batch * 64 floats
   az_launch(mse_kernel, dim3(gx, batch), dim3(256), 0, st, batch, C, HW, (const bf16_t*)pred, ldp, (const float*)target_f32,
                      (const float*)w, grad_scale, (float*)scratch_f32, (bf16_t*)dpred, cpad);
+  AZ_CHECK_LAUNCH();
+  az_launch(mse_finalize_kernel, dim3(1), dim3(64), 0, st, batch, C, HW, gx, (const float*)scratch_f32, (const float*)w,
+                     (float*)loss_out, (float*)per_sample_out);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+int az_robust_loss_fwd_bwd(int kind, int batch, int C, int HW, const void* pred, long ldp, const void* target_f32, const void* w,
+                           const void* c, float grad_scale, void* loss_out, void* per_sample_out, void* dpred, int cpad,
+                           void* scratch_f32, void* stream) {
+  if (kind < 1 || kind > 3 || batch <= 0 || batch > 4096 || C <= 0 || HW <= 0 || ldp < C || cpad < C || (kind != 1 && !c) || !pred ||
+      !target_f32 || !w || !loss_out || !per_sample_out || !scratch_f32)
+    return AZ_ERR_ARG(78);
+  hipStream_t st = (hipStream_t)stream;
+  int gx = (HW + 255) / 256; if (gx > 64) gx = 64;          // scratch: batch * 64 floats
+  const int pvec = C == 4 && !(ldp & 3) && !((uintptr_t)pred & 7);
+  const int dvec = !dpred || !pvec ? 0 : (cpad == 8 && !((uintptr_t)dpred & 15)) ? 8 : (cpad == 4 && !((uintptr_t)dpred & 7)) ? 4 : 0;
+  auto kern = kind == 1 ? robust_loss_kernel<1> : kind == 2 ? robust_loss_kernel<2> : robust_loss_kernel<3>;
+  az_launch(kern, dim3(gx, batch), dim3(256), 0, st, batch, C, HW, (const bf16_t*)pred, ldp, (const float*)target_f32,
+                     (const float*)w, (const float*)c, grad_scale, (float*)scratch_f32, (bf16_t*)dpred, cpad, pvec, dvec);
   AZ_CHECK_LAUNCH();
   az_launch(mse_finalize_kernel, dim3(1), dim3(64), 0, st, batch, C, HW, gx, (const float*)scratch_f32, (const float*)w,
                      (float*)loss_out, (float*)per_sample_out);

@@ -660,6 +660,27 @@ def mse_loss_fwd_bwd(pred_nhwc, target, w, grad_scale, loss_out, per_sample, dpr
                _ptr(per_sample), _ptr(dpred), cpad if dpred is not None else C, _ptr(workspace(pred_nhwc.device).scratch), _stream())
 
 
+ROBUST_KINDS = {"l1": 1, "huber": 2, "smooth_l1": 3}
+
+
+def robust_loss_fwd_bwd(kind, pred_nhwc, target, w, c, grad_scale, loss_out, per_sample, dpred):
+    """az_robust_loss_fwd_bwd: kind "l1" | "huber" | "smooth_l1" (or 1..3), operands as mse_loss_fwd_bwd plus c, the per-sample width
+    (fp32 [B]; None for l1 only).  The squared error is mse_loss_fwd_bwd's: it is not a kind here."""
+    B, H, W, ldp = pred_nhwc.shape
+    C = target.shape[1]
+    _req(pred_nhwc.dtype == BF16 and pred_nhwc.is_contiguous() and target.dtype == F32 and target.is_contiguous() and
+         tuple(target.shape) == (B, C, H, W) and w.dtype == F32 and w.numel() == B and loss_out.dtype == F32 and
+         per_sample.dtype == F32 and per_sample.numel() == B, "robust loss operands")
+    if c is not None:
+        _req(c.dtype == F32 and c.numel() == B and c.is_contiguous(), "robust loss widths")
+    cpad = C
+    if dpred is not None:
+        _req(dpred.dtype == BF16 and dpred.is_contiguous() and tuple(dpred.shape[:3]) == (B, H, W), "dpred")
+        cpad = dpred.shape[3]
+    lib().call("az_robust_loss_fwd_bwd", int(ROBUST_KINDS.get(kind, kind)), B, C, H * W, _ptr(pred_nhwc), ldp, _ptr(target), _ptr(w), _ptr(c),
+               float(grad_scale), _ptr(loss_out), _ptr(per_sample), _ptr(dpred), cpad, _ptr(workspace(pred_nhwc.device).scratch), _stream())
+
+
 # ---------------------------------------------------------------------------------------------
 # optimizer
 # ---------------------------------------------------------------------------------------------

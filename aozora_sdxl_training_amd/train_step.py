@@ -3,6 +3,7 @@
     noise-mix + target (eps / v_prediction / rectified_flow)   train.py:2743-2758  -> az_noise_target
     pred = unet(...)                                            train.py:2760-2761  -> AozoraUNet.forward_nhwc
     loss = weighted_sdxl_mse_loss(pred, target, ts, curve)      train.py:2763       -> az_mse_loss_fwd_bwd
+                                                                (LOSS_TYPE l1 / huber / smooth_l1: az_robust_loss_fwd_bwd)
     (loss / GA).backward()                                      train.py:2765       -> AozoraUNet.backward_nhwc
 
 Inputs that the reference draws from device RNG (noise, RF jitter) are INPUTS here (drawn by the
@@ -20,6 +21,7 @@ import torch
 
 from . import ops
 from ._lib import lib, AozoraError
+from .loss import loss_widths, parse_loss_type
 from .schedule import ddpm_coef_tables
 from .unet import AozoraUNet
 from .streams import check as stream_check
@@ -32,14 +34,15 @@ MODES = {"epsilon": 0, "v_prediction": 1, "rectified_flow": 2}
 class _Bucket:
     """Static input/output buffers + captured graph for one (B, H, W, ctx_len) shape."""
 
-    def __init__(self, dev, B, C, H, W, L, ctx_dim, pooled_dim):
+    def __init__(self, dev, B, C, H, W, L, ctx_dim, pooled_dim, ncoef=4):
         self.lat = torch.empty(B, C, H, W, dtype=BF16, device=dev)
         self.noise = torch.empty(B, C, H, W, dtype=F32, device=dev)
         self.ctx = torch.empty(B, L, ctx_dim, dtype=BF16, device=dev)
         self.pooled = torch.empty(B, pooled_dim, dtype=BF16, device=dev)
-        self.host = [torch.empty(4, B, dtype=F32).pin_memory() for _ in range(2)]   # ca, cb, tcond, w (double-buffered)
+        # ca, cb, tcond, w (double-buffered); a fifth row, the width c_b, only under a loss that has one (huber / smooth_l1)
+        self.host = [torch.empty(ncoef, B, dtype=F32).pin_memory() for _ in range(2)]
         self.host_ev = [None, None]
-        self.dev = torch.empty(4, B, dtype=F32, device=dev)
+        self.dev = torch.empty(ncoef, B, dtype=F32, device=dev)
         self.x8 = torch.zeros(B, H, W, 8, dtype=BF16, device=dev)
         self.target = torch.empty(B, C, H, W, dtype=F32, device=dev)
         self.dpred8 = torch.zeros(B, H, W, 8, dtype=BF16, device=dev)
@@ -66,9 +69,12 @@ class _Bucket:
 class TrainStep:
     def __init__(self, unet: AozoraUNet, mode: str = "epsilon", grad_accum: int = 1, world_size: int = 1,
                  loss_curve: Optional[torch.Tensor] = None, use_graph: bool = True, latent_dtype=BF16,
-                 double_buffer: bool = False):
+                 double_buffer: bool = False, loss="MSE"):
         if mode not in MODES:
             raise ValueError(f"unknown prediction type {mode!r}")
+        # loss: a LOSS_TYPE string or a loss.LossSpec.  Its min-SNR factor is the CALLER's to fold into loss_curve (loss.fold_min_snr,
+        # as trainer.train does): nothing here reads it.
+        self.loss_spec = parse_loss_type(loss, mode)
         self.unet, self.mode, self.ga, self.world = unet, mode, int(grad_accum), int(world_size)
         self.use_graph = use_graph
         self.use_tape = unet.policy.host_tape
@@ -118,6 +124,8 @@ class TrainStep:
         h[3] = 1.0 if self.curve is None else self.curve[ts.clamp(0, self.curve.shape[0] - 1)]
         if weight_scale != 1.0:
             h[3] *= float(weight_scale)
+        if self.loss_spec.needs_c:
+            h[4] = loss_widths(self.loss_spec, self.mode, ts, jitter)
         if h.numel() <= 256:
             return h                              # rides in the arguments of the staging launch (_stage): no H2D copy, no event
         bk.dev.copy_(h, non_blocking=True)
@@ -188,8 +196,13 @@ class TrainStep:
         ops.noise_target(MODES[self.mode], bk.lat, bk.noise, bk.dev[0], bk.dev[1], bk.x8, bk.target)
         u.begin_step((B, H, W, bk.ctx.shape[1], bk.parity))
         pred = u.forward_nhwc(bk.x8, bk.dev[2], bk.ctx, bk.pooled, bk.tids)
-        ops.mse_loss_fwd_bwd(pred.t.view(B, H, W, C), bk.target, bk.dev[3], 1.0 / (self.ga * self.world), bk.loss,
-                             bk.per_sample, bk.dpred8)
+        if self.loss_spec.kind == "mse":
+            ops.mse_loss_fwd_bwd(pred.t.view(B, H, W, C), bk.target, bk.dev[3], 1.0 / (self.ga * self.world), bk.loss,
+                                 bk.per_sample, bk.dpred8)
+        else:
+            ops.robust_loss_fwd_bwd(self.loss_spec.kind, pred.t.view(B, H, W, C), bk.target, bk.dev[3],
+                                    bk.dev[4] if self.loss_spec.needs_c else None, 1.0 / (self.ga * self.world), bk.loss,
+                                    bk.per_sample, bk.dpred8)
         u.backward_nhwc(pred, bk.dpred8, after_tail=after_tail)
         bk.pred = pred.t
 
@@ -253,7 +266,7 @@ class TrainStep:
             u._defer_join = bool(defer_join)
             u._pool_parity = parity
             if key not in self._buckets:
-                bk = _Bucket(u.device, B, C, H, W, L, u.cfg.cross_attention_dim, u.cfg.pooled_dim)
+                bk = _Bucket(u.device, B, C, H, W, L, u.cfg.cross_attention_dim, u.cfg.pooled_dim, 5 if self.loss_spec.needs_c else 4)
                 bk.tids = torch.empty(B, 6, dtype=F32, device=u.device)
                 bk.parity = parity
                 self._buckets[key] = bk

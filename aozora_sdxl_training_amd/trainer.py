@@ -22,6 +22,7 @@ from . import checkpoint as ckpt
 from . import data as feed
 from .clip import clip_grad_norm_
 from .ema import EmaWeights, read_options as _ema_options
+from .loss import fold_min_snr, parse_loss_type
 from .optimizers import PagedAdamW8bit, RavenAdamW, TitanAdamW
 from .schedule import (CustomCurveLRScheduler, TimestepSampler, ddpm_alphas_cumprod, generate_noise, make_time_ids,
                        seeded_torch_generator, timestep_loss_curve_from_config, trainable_mask)
@@ -136,6 +137,9 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     master = _master_option(config)          # "master_weights" (not in the reference, absent = off); refusals before anything is allocated
     GA = int(config.GRADIENT_ACCUMULATION_STEPS)
     mode = getattr(config, "PREDICTION_TYPE", "epsilon")
+    # LOSS_TYPE (loss.parse_loss_type; the reference's GUI offers "MSE" only): read before anything is allocated.  It goes into nothing
+    # that is saved: a resumed run reads it from the preset again.
+    loss_spec = parse_loss_type(getattr(config, "LOSS_TYPE", "MSE"), mode)
     config.is_rectified_flow = (mode == "rectified_flow")
     micro_step = optimizer_step = 0
     model_to_load = Path(config.SINGLE_FILE_CHECKPOINT_PATH)
@@ -159,8 +163,11 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     params = [p for p in unet.parameters() if p.requires_grad]
     # the step object first: it creates the data-gradient stream, and the order in which a process creates its streams decides
     # which hardware queues they share (streams.py); the optimizer's copy / exchange streams come after it, as in bench.py
-    loss_curve = timestep_loss_curve_from_config(config, 1000)
-    step = TrainStep(unet, mode=mode, grad_accum=GA, world_size=world, loss_curve=loss_curve, use_graph=False)
+    loss_curve = fold_min_snr(timestep_loss_curve_from_config(config, 1000), loss_spec, mode)
+    step = TrainStep(unet, mode=mode, grad_accum=GA, world_size=world, loss_curve=loss_curve, use_graph=False, loss=loss_spec)
+    if rank == 0 and (loss_spec.kind != "mse" or loss_spec.min_snr_gamma is not None):
+        print(f"INFO: LOSS_TYPE: {loss_spec.describe()}: an option outside the reference; the reported loss is this loss, not the squared error.  "
+              "(A LOSS_TYPE this build cannot read used to train MSE without a word and is now refused.)")
     from .dist import ShardedRaven, ShardedTitan
     titan = kind == "titan"
     # Single-GPU Titan: the device-accumulator form (dist.ShardedTitan in a group of one: fp32 gradient accumulator in HBM, the same
@@ -514,6 +521,11 @@ def main(argv=None) -> int:
         return 2
     if config.MIXED_PRECISION != "bfloat16":
         print(f"ERROR: MIXED_PRECISION={config.MIXED_PRECISION!r}: the HIP step computes in bf16 only.")
+        return 2
+    try:
+        parse_loss_type(getattr(config, "LOSS_TYPE", "MSE"), getattr(config, "PREDICTION_TYPE", "epsilon"))
+    except ValueError as e:
+        print(f"ERROR: {e}.")
         return 2
     if str(config.OPTIMIZER_TYPE).lower() not in ("raven", "titan", "paged_adamw_8bit"):
         raise ValueError(f"Unsupported optimizer type: '{config.OPTIMIZER_TYPE}'")          # train.py:2290

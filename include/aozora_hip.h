@@ -328,6 +328,15 @@ int az_noise_target(int mode, int batch, int C, int HW, int cpad, const void* la
 int az_mse_loss_fwd_bwd(int batch, int C, int HW, const void* pred, long ldp, const void* target_f32, const void* w,
                         float grad_scale, void* loss_out, void* per_sample_out, void* dpred, int cpad, void* scratch_f32,
                         void* stream);
+/* Robust losses in the place of the squared error (LOSS_TYPE; an option outside the reference): kind 1 l1 |x|, 2 huber
+ * 2c x^2 / (sqrt(x^2+c^2) + c), 3 smooth_l1 2 x^2 / (sqrt(x^2+c^2) + c), x = float(pred) - target, c fp32 [B] the per-sample width
+ * (null only for kind 1).  per_sample = mean over (C, HW) of l, loss = (1/B) sum_b w_b per_sample_b,
+ * dpred = bf16(grad_scale w_b / (C HW B) * l'(x)).  Operands, padding, scratch and summation order as az_mse_loss_fwd_bwd; the squared
+ * error is not a kind of this entry.  Refused: kind outside 1..3, cpad < C, ldp < C, a null c for kinds 2 and 3. */
+/* ref: train.py:2408-2416, train.py:2763-2765 (the loss seam; the reference has the squared error only) */
+int az_robust_loss_fwd_bwd(int kind, int batch, int C, int HW, const void* pred, long ldp, const void* target_f32, const void* w,
+                           const void* c, float grad_scale, void* loss_out, void* per_sample_out, void* dpred, int cpad,
+                           void* scratch_f32, void* stream);
 
 /* ---- optimizer (raven.py:89-149, titan.py:119-131,162-184,230-296; clip train.py:2771-2781) ------- */
 /* sum of squares of n bf16 grads -> out_f32[0] (accumulate=1 adds to existing value) */
