@@ -45,6 +45,17 @@ class AozoraError(RuntimeError):
     pass
 
 
+# A process that uses this library holds device objects (tensors, events, streams, contexts), many of them in reference cycles that
+# wait for the garbage collector (an AozoraUNet and its parameters, an optimizer and its timing span).  A fork()ed child -- a
+# multiprocessing.Manager server, a data-loader worker -- inherits that garbage but not a usable HIP runtime: were its collector to
+# finalize an inherited device object there, the destructor would call into a runtime that does not exist in the child.  gc.freeze()
+# in the child moves everything inherited into the permanent generation: the child collects its own garbage only and never runs the
+# parent's finalizers.
+if hasattr(os, "register_at_fork"):
+    import gc
+    os.register_at_fork(after_in_child=gc.freeze)
+
+
 # The operations of a launch tape (tape.py), one kind each.  Events and streams travel as objects (ForkEvent / torch.cuda.Event,
 # torch.cuda.Stream), not as raw handles: the Python replay issues torch events through torch, and a tape keeps them alive.
 class Call(NamedTuple):         # an entry point of the C ABI

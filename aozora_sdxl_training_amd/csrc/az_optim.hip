@@ -261,6 +261,116 @@ __global__ void adamw_wide_kernel(long n, P par, const TG* __restrict__ g, TM* _
   }
 }
 
+// ---- parameter groups (an option the reference's trainer does not use: INTEGRATION.md "Parameter groups") -----------------------------
+// az_adamw_flat_seg: wd_factor and step_size of an element come from ITS group; everything else (adamw_math included) is shared with
+// the kernels above.  PlainParam: the bf16 parameter of adamw_kernel as a policy of the wide form, round to nearest even.
+struct PlainParam {
+  bf16_t* p;
+  __device__ __forceinline__ void load8(long i, float* x) const { ::load8<bf16_t>(p + i, x); }
+  __device__ __forceinline__ float load(long i) const { return bf2f(p[i]); }
+  __device__ __forceinline__ void store8(long i, const float* x) const { store8_moment<bf16_t>(p + i, x); }
+  __device__ __forceinline__ void store(long i, float x) const { p[i] = f2bf(x); }
+};
+// Global element e belongs to the first segment s with end[s] > e (ends ascending, exclusive); its group is gid[s], whose values are
+// gh[2 * gid] = wd_factor, gh[2 * gid + 1] = step_size.  Every index is clamped: s to [0, nseg), gid to [0, ngroups) -- whatever the
+// tables hold, nothing outside them is read (an element past the last end takes the last segment).
+struct SegTab {
+  const long* __restrict__ end;
+  const int* __restrict__ gid;
+  const float* __restrict__ gh;
+  int nseg, ngroups;
+  long elem0;        // global index of the call's first element
+};
+// first s in [lo, hi] with end[s] > e; hi when there is none.  0 <= lo <= hi < nseg: reads end[lo .. hi - 1] only
+__device__ __forceinline__ int seg_find(const SegTab& t, long e, int lo, int hi) {
+  while (lo < hi) {
+    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
+    if (t.end[mid] > e) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+// The same lookups with WAVE-UNIFORM operands, read through the constant address space: the tables are never written while a kernel
+// runs, and saying so lets the compiler use scalar loads -- they run on the scalar unit and its own counter, beside the vector loads
+// of the operands instead of in a queue behind them.
+#define AZ_CONST_AS __attribute__((address_space(4)))
+__device__ __forceinline__ long seg_end_u(const SegTab& t, int s) { return ((const AZ_CONST_AS long*)(uintptr_t)t.end)[s]; }
+__device__ __forceinline__ int seg_find_u(const SegTab& t, long e, int lo, int hi) {
+  while (lo < hi) {
+    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
+    if (seg_end_u(t, mid) > e) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+__device__ __forceinline__ void seg_enter_u(const SegTab& t, int s, AdamwK& k) {
+  int g = ((const AZ_CONST_AS int*)(uintptr_t)t.gid)[s];
+  g = g < 0 ? 0 : (g >= t.ngroups ? t.ngroups - 1 : g);
+  const AZ_CONST_AS float* gh = (const AZ_CONST_AS float*)(uintptr_t)t.gh;
+  k.wdf = gh[2 * g]; k.step = gh[2 * g + 1];
+}
+__device__ __forceinline__ long uniform64(long x) {            // x holds the same value in every lane: tell the compiler
+  return (long)(((unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned long)x >> 32)) << 32) |
+                (unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)x));
+}
+// the group values of segment s into k, and the first element that is no longer in s (the last segment never ends)
+__device__ __forceinline__ long seg_enter(const SegTab& t, int s, AdamwK& k) {
+  int g = t.gid[s];
+  g = g < 0 ? 0 : (g >= t.ngroups ? t.ngroups - 1 : g);
+  k.wdf = t.gh[2 * g]; k.step = t.gh[2 * g + 1];
+  return s == t.nseg - 1 ? 0x7FFFFFFFFFFFFFFFL : t.end[s];
+}
+
+// The split of adamw_wide_kernel.  The 64 groups of a wave are consecutive, so the wave brackets the segments it touches with uniform
+// operands (seg_find_u: scalar loads, under the operand loads already in flight): [lo, hi] is ONE segment almost always -- the table
+// of an AozoraUNet has segments of >= 64 elements and a wave covers 512 -- and the wave then runs the wide kernel's loop body with
+// that segment's two values.  Otherwise a lane searches the bracket only, and walks forward inside its 8 elements where a segment
+// ends among them.
+template <typename TM, typename TG, typename P>
+__global__ void adamw_seg_kernel(long n, P par, const TG* __restrict__ g, TM* __restrict__ m, TM* __restrict__ v,
+                                 const float* __restrict__ hyper, const float* __restrict__ coef, Split s, SegTab t) {
+  const AdamwK k = adamw_consts(hyper, coef);
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long)gridDim.x * blockDim.x;
+  const long body = s.head + (s.groups << 3);               // <= n (split_for)
+  const int last = t.nseg - 1;
+  for (long gi = tid; gi < s.groups; gi += nthr) {
+    const long i = s.head + (gi << 3), e0 = t.elem0 + i;
+    float gg[8], mm[8], vv[8], pp[8];                         // issued first: the searches run under these loads
+    load8<TG>(g + i, gg); load8<TM>(m + i, mm); load8<TM>(v + i, vv); par.load8(i, pp);
+    const long gf = uniform64(gi - (long)(threadIdx.x & 63));  // the wave's first group (lane 0 is active whenever any lane is)
+    const long gl = gf + 63 < s.groups ? gf + 63 : s.groups - 1;
+    const long el = t.elem0 + s.head + (gl << 3) + 7;         // the wave's last element
+    const int lo = seg_find_u(t, t.elem0 + s.head + (gf << 3), 0, last);
+    const int hi = lo < last && seg_end_u(t, lo) <= el ? seg_find_u(t, el, lo + 1, last) : lo;
+    AdamwK ke = k;
+    if (lo == hi) {
+      seg_enter_u(t, lo, ke);
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        adamw_math<TG>(ke, [&] { return gg[e]; }, [&] { return mm[e]; }, [&] { return vv[e]; }, [&] { return pp[e]; }, mm[e], vv[e], pp[e]);
+    } else {
+      int sg = seg_find(t, e0, lo, hi);
+      long end = seg_enter(t, sg, ke);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if (e0 + e >= end) {                                  // (never for e == 0: end > e0 or sg is the last segment)
+          while (sg < last && t.end[sg] <= e0 + e) ++sg;
+          end = seg_enter(t, sg, ke);
+        }
+        adamw_math<TG>(ke, [&] { return gg[e]; }, [&] { return mm[e]; }, [&] { return vv[e]; }, [&] { return pp[e]; }, mm[e], vv[e], pp[e]);
+      }
+    }
+    par.store8(i, pp);
+    store8_moment<TM>(m + i, mm);
+    store8_moment<TM>(v + i, vv);
+  }
+  const long nscalar = n - (s.groups << 3);                  // head + tail
+  for (long j = tid; j < nscalar; j += nthr) {
+    const long i = j < s.head ? j : j - s.head + body;
+    AdamwK ke = k;
+    seg_enter(t, seg_find(t, t.elem0 + i, 0, last), ke);
+    adamw_elem<TM, TG>(ke, i, g, m, v, [&] { return par.load(i); }, [&](float pp) { par.store(i, pp); });
+  }
+}
+
 template <typename TG>
 __global__ void offload_kernel(long n, const TG* __restrict__ g, float* __restrict__ gh, int accumulate) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -348,6 +458,20 @@ int launch_adamw_sr(long n, void* p, const void* g, int gdtype, void* m, void* v
   const SrArgs sr = {(uint32_t)(unsigned long)seed, (uint32_t)((unsigned long)seed >> 32), (uint32_t)step, (uint32_t)domain, elem0};
   const Split s = split_for(n, {{p, 2}, {g, gsz}, {m, esz}, {v, esz}}, (8 - (elem0 & 7)) & 7);
   return launch_adamw(n, SrParam{(bf16_t*)p, sr}, s, g, gdtype, m, v, mdtype, hyper, coef, st);
+}
+
+template <typename P>
+int launch_adamw_seg(long n, P par, Split s, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper, const void* coef,
+                     const SegTab& t, hipStream_t st) {
+  dim3 grid(grid_for(n, s)), blk(256);
+  const float* hy = (const float*)hyper; const float* cf = (const float*)coef;
+  const bool ok = adamw_dispatch(mdtype, gdtype, [&](auto tm, auto tg) {
+    typedef typename decltype(tm)::type TM; typedef typename decltype(tg)::type TG;
+    az_launch((adamw_seg_kernel<TM, TG, P>), grid, blk, 0, st, n, par, (const TG*)g, (TM*)m, (TM*)v, hy, cf, s, t);
+  });
+  if (!ok) return AZ_ERR_ARG(79);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
 }
 
 // ---- fp32 exponential moving average of the bf16 parameters (an option the reference does not have: INTEGRATION.md) -------------------
@@ -519,6 +643,32 @@ int az_adamw_flat_master(long n, void* p, void* w_f32, const void* g, int gdtype
   if (n == 0) return AZ_OK;
   const Split s = split_for(n, {{p, 2}, {w_f32, 4}, {g, gmask + 1}, {m, emask + 1}, {v, emask + 1}});
   return launch_adamw(n, MasterParam{(bf16_t*)p, (float*)w_f32}, s, g, gdtype, m, v, mdtype, hyper, coef, (hipStream_t)stream);
+}
+
+int az_adamw_flat_seg(long n, void* p, void* w_f32, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper,
+                      const void* coef, const void* seg_end, const void* seg_gid, long nseg, const void* ghyper, int ngroups, long elem0,
+                      int rounding, long seed, long step, long domain, void* stream) {
+  if (n < 0 || !p || !g || !m || !v || !hyper || !seg_end || !seg_gid || !ghyper || nseg <= 0 || nseg > 0x7FFFFFFFL || ngroups <= 0 ||
+      ngroups > 255 || elem0 < 0 || mdtype < 0 || mdtype > 2 || gdtype < 0 || gdtype > 1 || rounding < 0 || rounding > 1 || (w_f32 && rounding))
+    return AZ_ERR_ARG(79);
+  const uintptr_t emask = mdtype == 1 ? 3 : 1, gmask = gdtype == 0 ? 1 : 3;
+  if (((uintptr_t)p & 1) || ((uintptr_t)w_f32 & 3) || ((uintptr_t)g & gmask) || ((uintptr_t)m & emask) || ((uintptr_t)v & emask) ||
+      ((uintptr_t)seg_end & 7) || ((uintptr_t)seg_gid & 3) || ((uintptr_t)ghyper & 3))
+    return AZ_ERR_ARG(80);
+  if (n == 0) return AZ_OK;
+  const SegTab t = {(const long*)seg_end, (const int*)seg_gid, (const float*)ghyper, (int)nseg, ngroups, elem0};
+  hipStream_t st = (hipStream_t)stream;
+  if (w_f32) {
+    const Split s = split_for(n, {{p, 2}, {w_f32, 4}, {g, gmask + 1}, {m, emask + 1}, {v, emask + 1}});
+    return launch_adamw_seg(n, MasterParam{(bf16_t*)p, (float*)w_f32}, s, g, gdtype, m, v, mdtype, hyper, coef, t, st);
+  }
+  if (rounding) {           // a group of 8 is a Philox group: (elem0 + i) % 8 == 0 there (launch_adamw_sr)
+    const SrArgs sr = {(uint32_t)(unsigned long)seed, (uint32_t)((unsigned long)seed >> 32), (uint32_t)step, (uint32_t)domain, elem0};
+    const Split s = split_for(n, {{p, 2}, {g, gmask + 1}, {m, emask + 1}, {v, emask + 1}}, (8 - (elem0 & 7)) & 7);
+    return launch_adamw_seg(n, SrParam{(bf16_t*)p, sr}, s, g, gdtype, m, v, mdtype, hyper, coef, t, st);
+  }
+  const Split s = split_for(n, {{p, 2}, {g, gmask + 1}, {m, emask + 1}, {v, emask + 1}});
+  return launch_adamw_seg(n, PlainParam{(bf16_t*)p}, s, g, gdtype, m, v, mdtype, hyper, coef, t, st);
 }
 
 int az_raven_step_ex(long n, void* p, const void* g, int gdtype, void* m_host, void* v_host, int mdtype, const void* hyper,

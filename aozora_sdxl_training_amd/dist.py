@@ -119,15 +119,22 @@ class ShardedRaven:
 
     master_weights (not in the reference, False = off): `self.w_dev`, one fp32 device buffer in the layout of m_dev / v_dev, holds the
     master copy of this rank's owned trainable elements; the update reads and writes it and pflat receives bf16(master)
-    (az_adamw_flat_master; INTEGRATION.md "fp32 master weights").  Whoever writes parameters from outside calls resync_master()."""
+    (az_adamw_flat_master; INTEGRATION.md "fp32 master weights").  Whoever writes parameters from outside calls resync_master().
+
+    groups (not used by the reference's trainer, None = off): a param_groups.Resolved -- the segment table over the flat buffer and the
+    (lr_scale, weight_decay) of every group, group 0 the base.  Every owned range is still updated by ONE launch (az_adamw_flat_seg;
+    INTEGRATION.md "Parameter groups"); param_groups[0] stays the one group the scheduler writes.  Not with state_on_host."""
 
     def __init__(self, unet, lr=8e-7, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, debias_strength=0.3,
                  momentum_dtype=torch.bfloat16, clip_grad_norm=1.0, process_group=None, force_local=False,
                  overlap=True, regions: Optional[int] = None, force_exchange=False, state_on_host=False,
-                 stochastic_rounding: bool = False, sr_seed: int = 0, ema=None, master_weights: bool = False):
+                 stochastic_rounding: bool = False, sr_seed: int = 0, ema=None, master_weights: bool = False, groups=None):
         import torch.distributed as dist
         if master_weights and stochastic_rounding:
             raise ValueError(MASTER_SR_REFUSAL)
+        if groups is not None and state_on_host:
+            from .param_groups import HOST_PATH_REFUSAL
+            raise ValueError(HOST_PATH_REFUSAL.format(what="state_on_host = True"))
         self.unet = unet
         # stochastic rounding of the bf16 write-back (not in the reference, off by default: optimizers.RavenAdamW): the random bits are
         # keyed by (sr_seed, step_count, offset in the flat buffer), so regions, rank shards and RavenAdamW's ranges all draw the same
@@ -205,6 +212,18 @@ class ShardedRaven:
         self._prefetched = False
         self.hyper_host = torch.zeros(8, dtype=torch.float32).pin_memory()
         self.hyper_dev = torch.zeros(8, dtype=torch.float32, device=dev)
+        # parameter groups (param_groups.Resolved; not in the reference's trainer, None = off: no launch, allocation or event differs):
+        # the segment tables go to the device once; [wd_factor, step_size] of every group follows the hyper vector each step (_hyper).
+        # param_groups[0] stays the base group the scheduler writes; the groups scale ITS lr.
+        self.groups = None
+        if groups is not None:
+            self.groups = [(float(s_), float(wd_)) for s_, wd_ in groups.groups]
+            if self.groups[0] != (1.0, float(weight_decay)):
+                raise ValueError("groups: group 0 must be the base group (lr_scale 1, the optimizer's own weight_decay)")
+            self.seg_end_dev, self.seg_gid_dev = ops.upload_group_tables(groups.seg_end, groups.seg_gid, len(self.groups),
+                                                                         [r for rs in self.ranges for r in rs], dev)
+            self.ghyper_host = torch.zeros(len(self.groups), 2, dtype=torch.float32).pin_memory()
+            self.ghyper_dev = torch.zeros(len(self.groups), 2, dtype=torch.float32, device=dev)
         self.scal = torch.zeros(8, dtype=torch.float32, device=dev)     # [0] sumsq [1] coef [2] norm
         from .streams import host_link_streams
         self.copy_streams = host_link_streams(dev)      # bound to their SDMA engines before any RCCL communicator exists (streams.py)
@@ -340,6 +359,10 @@ class ShardedRaven:
             self._ev.synchronize()
         self.hyper_host.copy_(torch.tensor([lr, b1, b2, eps, wdf, lr / bc1, math.sqrt(bc2), 0.0], dtype=torch.float32))
         self.hyper_dev.copy_(self.hyper_host, non_blocking=True)
+        if self.groups is not None:          # the same doubles, the same single rounding to fp32, the same pinned-buffer discipline
+            from .param_groups import ghyper_rows
+            self.ghyper_host.copy_(torch.tensor(ghyper_rows(self.groups, lr, bc1), dtype=torch.float32))
+            self.ghyper_dev.copy_(self.ghyper_host, non_blocking=True)
         self._ev = torch.cuda.Event(); self._ev.record()
 
     def prefetch(self):
@@ -433,7 +456,9 @@ class ShardedRaven:
             ops.adamw_range(b - a, u.pflat.data_ptr() + a * 2, gbuf.data_ptr() + a * gsz, gdtype, self.m_dev.data_ptr() + hoff * esz,
                             self.v_dev.data_ptr() + hoff * esz, self.mdt, self.hyper_dev.data_ptr(), self.scal[1:2].data_ptr(), stream.cuda_stream,
                             master=self.w_dev.data_ptr() + hoff * 4 if self.master else None,
-                            sr=(self.sr_seed, self.step_count, 0, a) if self.sr else None)
+                            sr=(self.sr_seed, self.step_count, 0, a) if self.sr else None,
+                            **({} if self.groups is None else dict(groups=(self.seg_end_dev.data_ptr(), self.seg_gid_dev.data_ptr(),
+                                                                          self.seg_end_dev.numel(), self.ghyper_dev.data_ptr(), len(self.groups), a))))
 
     def _gather_regions(self, regions):
         """On the communication stream (current), per region: all-gather, then its W^T copies, then an event -> [(region, event)]."""

@@ -709,7 +709,7 @@ def ema_flat(p, ema, one_minus_decay, stream=None):
 MOMENT_CODE = {BF16: 0, F32: 1, torch.float16: 2}      # mdtype of the C ABI
 
 
-def adamw_range(n, p, g, gdtype, m, v, mdtype, hyper, coef, stream, *, master=None, sr=None, host_pipeline=None):
+def adamw_range(n, p, g, gdtype, m, v, mdtype, hyper, coef, stream, *, master=None, sr=None, host_pipeline=None, groups=None):
     """The Raven / Titan AdamW update of ONE flat range of n elements -- the one place that names the az_adamw_flat* / az_raven_step*
     entry points.  Everything is a raw address or handle (optimizers.RavenAdamW works on storage spans, not tensors), checked by the
     caller: p bf16 parameters, g gradients (gdtype 0 bf16, 1 fp32), m / v moments of torch dtype `mdtype`, hyper the fp32 vector of
@@ -718,11 +718,24 @@ def adamw_range(n, p, g, gdtype, m, v, mdtype, hyper, coef, stream, *, master=No
       sr=(seed, step, domain, elem0)                                   stochastic rounding of the bf16 write (az_adamw_flat_sr)
       host_pipeline=(staging address, chunk_elems, h2d stream, d2h stream)    m / v are PINNED HOST memory, streamed in chunks through
                                the device staging buffer on the two copy streams (az_raven_step_ex / az_raven_step_sr)
-    master combines with neither of the other two: no entry point."""
+      groups=(seg_end address, seg_gid address, nseg, ghyper address, ngroups, elem0)      parameter groups: wd_factor and step_size
+                               per element from the segment tables (GroupTables.args), everything in ONE launch (az_adamw_flat_seg);
+                               with master or sr too, elem0 the global index of the range's first element (sr names the same one)
+    master combines with neither of sr / host_pipeline, groups not with host_pipeline: no entry point."""
     if master is not None and (sr is not None or host_pipeline is not None):
         raise AozoraError("adamw_range: master weights combine with neither stochastic rounding nor the pinned-host pipeline")
+    if groups is not None and host_pipeline is not None:
+        raise AozoraError("adamw_range: parameter groups do not combine with the pinned-host pipeline (no segmented form of the chunk pipeline)")
     vp = ctypes.c_void_p
     rest = (vp(g), int(gdtype), vp(m), vp(v), MOMENT_CODE[mdtype], vp(hyper), vp(coef or 0))
+    if groups is not None:
+        seg_end, seg_gid, nseg, ghyper, ngroups, elem0 = groups
+        if sr is not None and int(sr[3]) != int(elem0):
+            raise AozoraError("adamw_range: stochastic rounding and the segment lookup must name the same global element index")
+        seed, step, domain = (int(x) for x in sr[:3]) if sr is not None else (0, 0, 0)
+        lib().call("az_adamw_flat_seg", int(n), vp(p), vp(master or 0), *rest, vp(seg_end), vp(seg_gid), int(nseg), vp(ghyper), int(ngroups),
+                   int(elem0), int(sr is not None), seed, step, domain, vp(stream))
+        return
     sr = tuple(int(x) for x in sr) if sr is not None else ()
     if master is not None:
         lib().call("az_adamw_flat_master", int(n), vp(p), vp(master), *rest, vp(stream))
@@ -732,6 +745,24 @@ def adamw_range(n, p, g, gdtype, m, v, mdtype, hyper, coef, stream, *, master=No
         staging, chunk_elems, h2d, d2h = host_pipeline
         lib().call("az_raven_step_sr" if sr else "az_raven_step_ex", int(n), vp(p), *rest, vp(staging), int(chunk_elems), vp(stream), vp(h2d),
                    vp(d2h), *sr)
+
+
+def check_group_tables(seg_end, seg_gid, ngroups, ranges=()):
+    """The host copy of a segment table (adamw_range's groups=) before it is uploaded: as many ids as ends, ends ascending, ids in
+    [0, ngroups), 1 <= ngroups <= 255, and every updated range [a, b) of `ranges` inside [0, last end)."""
+    seg_end, seg_gid = [int(x) for x in seg_end], [int(x) for x in seg_gid]
+    _req(len(seg_end) > 0 and len(seg_end) == len(seg_gid), "segment table: seg_end and seg_gid need one entry per segment, at least one")
+    _req(1 <= int(ngroups) <= 255, "segment table: 1 to 255 groups")
+    _req(seg_end[0] > 0 and all(a < b for a, b in zip(seg_end, seg_end[1:])), "segment table: ends must be positive and strictly ascending")
+    _req(all(0 <= g < int(ngroups) for g in seg_gid), "segment table: a group id outside [0, number of groups)")
+    _req(all(0 <= a <= b <= seg_end[-1] for a, b in ranges), "segment table: an updated range is not covered by the segments")
+    return seg_end, seg_gid
+
+
+def upload_group_tables(seg_end, seg_gid, ngroups, ranges, device):
+    """check_group_tables, then the two tables on `device` once (they never change during a run) -> (int64 ends, int32 ids)."""
+    seg_end, seg_gid = check_group_tables(seg_end, seg_gid, ngroups, ranges)
+    return torch.tensor(seg_end, dtype=torch.int64).to(device), torch.tensor(seg_gid, dtype=torch.int32).to(device)
 
 
 def adamw_flat_master(p, w, g, m, v, hyper, coef=None, stream=None):

@@ -23,6 +23,7 @@ from . import data as feed
 from .clip import clip_grad_norm_
 from .ema import EmaWeights, read_options as _ema_options
 from .loss import fold_min_snr, parse_loss_type
+from . import param_groups as pgroups
 from .optimizers import PagedAdamW8bit, RavenAdamW, TitanAdamW
 from .schedule import (CustomCurveLRScheduler, TimestepSampler, ddpm_alphas_cumprod, generate_noise, make_time_ids,
                        seeded_torch_generator, timestep_loss_curve_from_config, trainable_mask)
@@ -105,8 +106,11 @@ def _master_option(config) -> bool:
     return True
 
 
-def _optimizer_8bit(config, params):
-    """create_optimizer (train.py:2271-2288): PagedAdamW8bit from PAGED_ADAMW_8BIT_PARAMS at lr = max(curve), min_8bit_size 4096."""
+def _optimizer_8bit(config, params, groups=None):
+    """create_optimizer (train.py:2271-2288): PagedAdamW8bit from PAGED_ADAMW_8BIT_PARAMS at lr = max(curve), min_8bit_size 4096.
+    groups (param_groups.Resolved, None = off; not in the reference's trainer): one torch group per resolved group with its lr_scale (the
+    scheduler scales it, train.py:347-352) and weight_decay, the BASE group last -- the loop reports param_groups[-1]["lr"], the curve's
+    unscaled value.  The kernel takes per-group hyper-parameters in its one launch already."""
     curve = getattr(config, "LR_CUSTOM_CURVE", [])
     lr = max(p[1] for p in curve) if curve else config.LEARNING_RATE
     hp = {**_ADAMW8_DEFAULTS, **dict(getattr(config, "PAGED_ADAMW_8BIT_PARAMS", {}) or {})}
@@ -114,6 +118,12 @@ def _optimizer_8bit(config, params):
         raise ValueError(_SR_8BIT_REFUSAL)
     if "master_weights" in hp:
         raise ValueError(_MASTER_8BIT_REFUSAL)
+    if groups is not None:
+        members = [[] for _ in groups.groups]
+        for p in params:
+            members[groups.param_gid[p._az_name]].append(p)
+        order = list(range(1, len(groups.groups))) + [0]
+        params = [{"params": members[g], "lr_scale": groups.groups[g][0], "weight_decay": groups.groups[g][1]} for g in order]
     return PagedAdamW8bit(params, lr=lr, betas=tuple(hp["betas"]), eps=hp["eps"], weight_decay=hp["weight_decay"], min_8bit_size=4096)
 
 
@@ -135,6 +145,10 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     # reference, absent = off).  Read first: an invalid value is refused before anything is allocated.
     ema_decay, ema_warmup = _ema_options(getattr(config, {"titan": "TITAN_PARAMS", "paged_adamw_8bit": "PAGED_ADAMW_8BIT_PARAMS"}.get(kind, "RAVEN_PARAMS"), None))
     master = _master_option(config)          # "master_weights" (not in the reference, absent = off); refusals before anything is allocated
+    # "param_groups" in the active optimizer's dictionary (param_groups.py; not in the reference's trainer, absent or [] = off): the rules
+    # are read, and what they do not combine with refused, before anything is allocated.  Like LOSS_TYPE they go into nothing that is
+    # saved: a resumed run reads them from the preset again.
+    group_rules = pgroups.option(config)
     GA = int(config.GRADIENT_ACCUMULATION_STEPS)
     mode = getattr(config, "PREDICTION_TYPE", "epsilon")
     # LOSS_TYPE (loss.parse_loss_type; the reference's GUI offers "MSE" only): read before anything is allocated.  It goes into nothing
@@ -161,6 +175,11 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     for (n, p), m in zip(unet.named_parameters(), trainable_mask(names, [k for k in excl if k])):
         p.requires_grad = m                                                          # train.py:2664-2667
     params = [p for p in unet.parameters() if p.requires_grad]
+    # the rules against the trainable parameters (a rule that matches none is refused: a typo must not silently train the default)
+    groups = None
+    if group_rules:
+        hp_g = dict(getattr(config, {"titan": "TITAN_PARAMS", "paged_adamw_8bit": "PAGED_ADAMW_8BIT_PARAMS"}.get(kind, "RAVEN_PARAMS"), None) or {})
+        groups = pgroups.resolve_unet(unet, group_rules, hp_g.get("weight_decay", (_ADAMW8_DEFAULTS if eightbit else _RAVEN_DEFAULTS)["weight_decay"]))
     # the step object first: it creates the data-gradient stream, and the order in which a process creates its streams decides
     # which hardware queues they share (streams.py); the optimizer's copy / exchange streams come after it, as in bench.py
     loss_curve = fold_min_snr(timestep_loss_curve_from_config(config, 1000), loss_spec, mode)
@@ -178,7 +197,7 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     host_titan = titan and not dp and bool(getattr(config, "TITAN_HOST_GRADIENTS", False))
     if eightbit:
         # one rank, the module-optimizer branch of the loop: expose_grads -> clip_grad_norm_ -> step (blockwise 8-bit AdamW in HIP)
-        optimizer = _optimizer_8bit(config, params)
+        optimizer = _optimizer_8bit(config, params, groups)
     elif not host_titan:
         # The flat fused optimizer (one rank: no collectives): m / v resident in HBM (or, RAVEN_STATE_ON_HOST, prefetched under the
         # window's last micro-step and written back under the next window), update of the whole flat range in one launch per
@@ -194,13 +213,19 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
             # m / v stay resident in HBM (10.3 GB of 288) unless the preset asks for the reference's residency -- pinned host memory,
             # streamed over the host link every optimizer step (raven.py:83-84, 114-117) -- with RAVEN_STATE_ON_HOST = true
             state_on_host=bool(getattr(config, "RAVEN_STATE_ON_HOST", False)), **_sr_args(config, hp),
-            ema=dict(decay=ema_decay, warmup=ema_warmup) if ema_decay is not None else None, **(dict(master_weights=True) if master else {}))
+            ema=dict(decay=ema_decay, warmup=ema_warmup) if ema_decay is not None else None, **(dict(master_weights=True) if master else {}),
+            **(dict(groups=groups) if groups is not None else {}))
     else:
         optimizer = _optimizer(config, params)
     if rank == 0 and getattr(optimizer, "sr", getattr(optimizer, "_sr", False)):
         print(f"INFO: stochastic rounding of the bf16 parameter update is ON (seed {int(getattr(config, 'SEED', 0) or 0)}): an option outside "
               "the reference; results differ from the default round-to-nearest write-back")
     flat_opt = isinstance(optimizer, ShardedRaven)
+    if rank == 0 and groups is not None:
+        print(f"INFO: parameter groups are ON ({len(groups.groups)} group(s), {len(groups.seg_end)} segment(s) of the flat buffer, one update "
+              "launch per contiguous range as without them): an option outside the reference; the reported learning rate is the curve's, unscaled")
+        for line in pgroups.describe(groups):
+            print(f"INFO: {line}: an option outside the reference")
     if rank == 0 and master:
         print(f"INFO: fp32 master weights are ON ({optimizer.w_dev.numel() * 4} bytes of fp32 on this rank): an option outside the reference; "
               "results differ from the default bf16-only update from the second optimizer step on")
@@ -524,6 +549,7 @@ def main(argv=None) -> int:
         return 2
     try:
         parse_loss_type(getattr(config, "LOSS_TYPE", "MSE"), getattr(config, "PREDICTION_TYPE", "epsilon"))
+        pgroups.option(config)
     except ValueError as e:
         print(f"ERROR: {e}.")
         return 2
@@ -576,6 +602,9 @@ def main(argv=None) -> int:
         unet = ckpt.load_unet(src, device, model_cfg)
     try:
         train(config, unet=unet, device=device)
+    except pgroups.GroupsError as e:         # a rule that matches no trainable parameter is only known once the model is loaded
+        print(f"ERROR: {e}.")
+        return 2
     finally:
         if world > 1:
             import torch.distributed as tdist

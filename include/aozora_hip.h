@@ -411,6 +411,22 @@ int az_ema_flat(long n, const void* p, void* ema_f32, float one_minus_decay, voi
 /* ref: raven.py:109-147 (the update with p32 kept between steps instead of p.copy_(p32) alone), titan.py:230-296 */
 int az_adamw_flat_master(long n, void* p, void* w_f32, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper,
                          const void* coef, void* stream);
+/* AdamW over a flat range whose elements belong to PARAMETER GROUPS with their own learning rate and weight decay (an option the
+ * reference's trainer does not use; off by default -- INTEGRATION.md "Parameter groups"): ONE launch for the range, however many
+ * groups alternate in it.  The call's element i has the global index e = elem0 + i and belongs to the first segment s with
+ * seg_end[s] > e (seg_end: device int64[nseg], ascending, exclusive ends; an element past the last end takes the last segment); its
+ * group is seg_gid[s] (device int32[nseg], clamped to [0, ngroups)), and it is updated with wd_factor = ghyper[2 * group] and
+ * step_size = ghyper[2 * group + 1] (device fp32[ngroups][2]) in place of hyper[4] and hyper[5]; beta1, beta2, eps and sqrt_bc2
+ * are hyper's.  The arithmetic is az_adamw_flat_ex's operation for operation; a segment may end anywhere, inside an aligned group
+ * of 8 elements too.  The parameter operand: w_f32 null and rounding 0 -- bf16 p, round to nearest even (az_adamw_flat_ex);
+ * rounding 1 -- stochastic rounding with (seed, step, domain, elem0) as az_adamw_flat_sr; w_f32 given -- the fp32 master of
+ * az_adamw_flat_master (rounding must be 0).  No lookup ever leaves the three tables, whatever they hold.  n == 0 returns 0 without
+ * a launch; n < 0, a null p / g / m / v / hyper / table, nseg <= 0, ngroups <= 0 or > 255, elem0 < 0, mdtype, gdtype or rounding out
+ * of range, or a pointer not aligned to its element are argument errors. */
+/* ref: raven.py:96-105 (the loop over param_groups with their own lr / weight_decay), train.py:347-352 (lr_scale per group) */
+int az_adamw_flat_seg(long n, void* p, void* w_f32, const void* g, int gdtype, void* m, void* v, int mdtype, const void* hyper,
+                      const void* coef, const void* seg_end, const void* seg_gid, long nseg, const void* ghyper, int ngroups,
+                      long elem0, int rounding, long seed, long step, long domain, void* stream);
 /* g_bf16[i] = bf16(g[i] * coef[0]) in place -- the in-place clip of torch.nn.utils.clip_grad_norm_
  * (train.py:2775-2778); skipped entirely when coef[0] == 1 */
 /* ref: train.py:2775-2778 (in-place gradient scaling of clip_grad_norm_) */
