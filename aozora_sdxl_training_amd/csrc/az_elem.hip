@@ -343,11 +343,27 @@ __global__ void nhwc_to_nchw_kernel(int B, int C, int HW, int lds, const bf16_t*
   }
 }
 
+// noise mix + target of one element: x the latent, nm the noise that enters the noisy latents, nt the noise the target is built
+// from (the same value everywhere but under NOISE_MODE's input perturbation).  The reference evaluates these expressions as
+// separate fp32 tensor ops and the bf16 result must match bit for bit: plain operators under `fp contract(off)` (no FMA fusion)
+__device__ __forceinline__ void noise_mix_target(int mode, float a, float s, float x, float nm, float nt, float& xt, float& tg) {
+#pragma clang fp contract(off)   // HIP's __fmul_rn/__fadd_rn are plain operators: forbid FMA fusion here
+  if (mode == 2) {                 // rectified flow: fp32 throughout (train.py:2749-2750)
+    float p1 = a * x, p2 = s * nm;
+    xt = p1 + p2; tg = nt - x;
+  } else {
+    // DDPM: coefficient (bf16) * latents (bf16) is a bf16 product in the reference dataflow
+    float p1 = bf2f(f2bf(a * x)), p2 = s * nm;
+    xt = p1 + p2;
+    if (mode == 1) { float q1 = a * nt, q2 = bf2f(f2bf(s * x)); tg = q1 - q2; } else tg = nt;
+  }
+}
+
 // one thread per (b, pixel): reads C channel planes (coalesced along pixels), writes one NHWC row
 __global__ void noise_target_kernel(int mode, int B, int C, int HW, int cpad, const bf16_t* __restrict__ lat,
                                     const float* __restrict__ noise, const float* __restrict__ ca, const float* __restrict__ cb,
                                     bf16_t* __restrict__ noisy, float* __restrict__ target) {
-#pragma clang fp contract(off)   // HIP's __fmul_rn/__fadd_rn are plain operators: forbid FMA fusion here
+#pragma clang fp contract(off)
   long n = (long)B * HW;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     long b = i / HW; long p = i - b * HW;
@@ -358,17 +374,126 @@ __global__ void noise_target_kernel(int mode, int B, int C, int HW, int cpad, co
         long si = (b * C + c) * HW + p;
         float x = bf2f(lat[si]); float nz = noise[si];
         float xt, tg;
-        // the reference evaluates these expressions as separate fp32 tensor ops and the bf16 result
-        // must match bit for bit: plain operators under `fp contract(off)` (no FMA fusion)
-        if (mode == 2) {                 // rectified flow: fp32 throughout (train.py:2749-2750)
-          float p1 = a * x, p2 = s * nz;
-          xt = p1 + p2; tg = nz - x;
-        } else {
-          // DDPM: coefficient (bf16) * latents (bf16) is a bf16 product in the reference dataflow
-          float p1 = bf2f(f2bf(a * x)), p2 = s * nz;
-          xt = p1 + p2;
-          if (mode == 1) { float q1 = a * nz, q2 = bf2f(f2bf(s * x)); tg = q1 - q2; } else tg = nz;
-        }
+        noise_mix_target(mode, a, s, x, nz, nz, xt, tg);
+        o = f2bf(xt);
+        target[si] = tg;
+      }
+      noisy[i * cpad + c] = o;
+    }
+  }
+}
+
+// ---- noise modes (NOISE_MODE: noise offset, pyramid noise, input perturbation; not in the reference) -----------------------------
+// noise_shape_kernel, in place over the fp32 noise [B][C][H][W]:
+//     u = eps + offset * o[b][c] + sum_{l = 1..nlev} weight_l * up_l(z_l)[b][c][y][x]
+// o fp32 [B][C] (null: no offset term).  The level fields z_l are one packed fp32 buffer, level l at table[4l] as [B][C][h_l][w_l];
+// table (device int32 [nlev][4]) holds offset, h_l, w_l and the bits of the fp32 weight_l = discount^l.  up_l is bilinear
+// resampling to (H, W) with half-pixel centres: the source row of output row y is max(((2y+1) h - H) / (2H), 0); tap index and
+// the two tap weights come from the INTEGER numerator -- y0 = num / (2H), fy = float(rem) / float(2H), gy = float(2H - rem) /
+// float(2H) -- so that no coordinate is rounded in fp32 and both weights carry one rounding each (1 - fy formed in fp32 would
+// inherit fy's absolute error); both taps are clamped to the field.  Plain fp32 operators, no contraction: tests/noise_ref.py
+// restates them one by one.  Roundings that reach one element of u: a tap weight (1), tap * weight (1), the row sum (1), times
+// the row weight (its own rounding and the product: 2), the column sum (1), times weight_l (its rounding on the host and the
+// product: 2), the sum into u (1) and the sums of the levels behind it (nlev - l): K = 8 + nlev (3 without levels: offset rounded
+// on the host, its product, its sum).
+// One thread per (b, pixel) over the C channel planes, coalesced along pixels; grid (blocks of the sample, B).  With `partial`
+// each block also leaves (sum u, sum u^2) of its elements at partial[b][block][0..1]: a thread's pixels and channels one after the
+// other, the wave butterfly, the block's waves in order (block_sum) -- a fixed order, no atomics, and a geometry that depends on
+// H * W alone, so that a sample's sums do not depend on the batch it is in.
+__global__ __launch_bounds__(256) void noise_shape_kernel(int C, int H, int W, float* __restrict__ noise, const float* __restrict__ o,
+                                                          float offset, const float* __restrict__ fields, long nfields,
+                                                          const int* __restrict__ table, int nlev, float* __restrict__ partial) {
+#pragma clang fp contract(off)
+  __shared__ float sh[16];
+  const int b = blockIdx.y;
+  const int HW = H * W;
+  const float dh = (float)(2 * H), dw = (float)(2 * W);
+  float s1 = 0.f, s2 = 0.f;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
+    const int y = p / W, x = p - y * W;
+    for (int c = 0; c < C; ++c) {
+      const long plane = (long)b * C + c;
+      const long si = plane * HW + p;
+      float u = noise[si];
+      if (o) u = u + offset * o[plane];
+      for (int l = 0; l < nlev; ++l) {
+        const int h = table[4 * l + 1], w = table[4 * l + 2];
+        const float wt = __int_as_float(table[4 * l + 3]);
+        int ny = (2 * y + 1) * h - H; if (ny < 0) ny = 0;
+        int nx = (2 * x + 1) * w - W; if (nx < 0) nx = 0;
+        int y0 = ny / (2 * H), x0 = nx / (2 * W);
+        const int ry = ny - y0 * 2 * H, rx = nx - x0 * 2 * W;
+        if (y0 > h - 1) y0 = h - 1;
+        if (x0 > w - 1) x0 = w - 1;
+        const int y1 = y0 + 1 < h ? y0 + 1 : h - 1, x1 = x0 + 1 < w ? x0 + 1 : w - 1;
+        const long base = (long)table[4 * l] + plane * h * w;
+        const long i00 = base + (long)y0 * w + x0, i01 = base + (long)y0 * w + x1;
+        const long i10 = base + (long)y1 * w + x0, i11 = base + (long)y1 * w + x1;
+        // (a table that does not describe `fields` reads zeros, never past the buffer)
+        const float f00 = (unsigned long)i00 < (unsigned long)nfields ? fields[i00] : 0.f;
+        const float f01 = (unsigned long)i01 < (unsigned long)nfields ? fields[i01] : 0.f;
+        const float f10 = (unsigned long)i10 < (unsigned long)nfields ? fields[i10] : 0.f;
+        const float f11 = (unsigned long)i11 < (unsigned long)nfields ? fields[i11] : 0.f;
+        const float fy = (float)ry / dh, gy = (float)(2 * H - ry) / dh;
+        const float fx = (float)rx / dw, gx = (float)(2 * W - rx) / dw;
+        const float t0 = f00 * gx, t1 = f01 * fx, b0 = f10 * gx, b1 = f11 * fx;
+        const float top = t0 + t1, bot = b0 + b1;
+        const float vt = top * gy, vb = bot * fy;
+        const float v = vt + vb;
+        u = u + wt * v;
+      }
+      noise[si] = u;
+      const float uu = u * u;
+      s1 = s1 + u; s2 = s2 + uu;
+    }
+  }
+  if (partial) {
+    const float a1 = block_sum(s1, sh);
+    const float a2 = block_sum(s2, sh);
+    if (threadIdx.x == 0) {
+      float* dst = partial + ((long)b * gridDim.x + blockIdx.x) * 2;
+      dst[0] = a1; dst[1] = a2;
+    }
+  }
+}
+
+// noise_target_kernel with two optional inputs.  partial (+ nblk): noise_shape_kernel's sums; every thread adds its sample's nblk
+// pairs in block order and normalises the noise by the sample's unbiased standard deviation about its mean,
+//     var_b = (S2 - S1 * (S1 / n)) / (n - 1),  n = C * HW,   r_b = 1 / sqrt(var_b),   eps' = u * r_b
+// (division and sqrtf correctly rounded: no fast-math).  The relative error of r_b is at most (A + 4) 2^-24, A the longest chain
+// of additions behind S2 (tests/noise_ref.py shape_chain): S2's (A + 1) 2^-24 and the three operations behind it are halved by
+// the square root, which adds its own rounding and the reciprocal's.  xi (+ perturb): the noise that enters the noisy latents is
+// eps' + perturb * xi; the target is built from eps'.  Roundings that reach an output: r_b (A + 4), u * r_b, perturb * xi, their
+// sum, then noise_mix_target's product and sum: K = A + 9.  With both null: noise_target_kernel, bit for bit.
+__global__ void noise_target_ex_kernel(int mode, int B, int C, int HW, int cpad, const bf16_t* __restrict__ lat,
+                                       const float* __restrict__ noise, const float* __restrict__ ca, const float* __restrict__ cb,
+                                       const float* __restrict__ partial, int nblk, const float* __restrict__ xi, float perturb,
+                                       bf16_t* __restrict__ noisy, float* __restrict__ target) {
+#pragma clang fp contract(off)
+  long n = (long)B * HW;
+  long rb_of = -1; float rb = 1.f;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    long b = i / HW; long p = i - b * HW;
+    float a = ca[b], s = cb[b];
+    if (partial && b != rb_of) {
+      float s1 = 0.f, s2 = 0.f;
+      for (int k = 0; k < nblk; ++k) { s1 = s1 + partial[(b * nblk + k) * 2]; s2 = s2 + partial[(b * nblk + k) * 2 + 1]; }
+      const float cnt = (float)C * (float)HW;
+      const float m2 = s1 * (s1 / cnt);
+      const float var = (s2 - m2) / (cnt - 1.0f);
+      rb = 1.0f / sqrtf(var);
+      rb_of = b;
+    }
+    for (int c = 0; c < cpad; ++c) {
+      bf16_t o = 0;
+      if (c < C) {
+        long si = (b * C + c) * HW + p;
+        float x = bf2f(lat[si]); float nt = noise[si];
+        if (partial) nt = nt * rb;
+        float nm = nt;
+        if (xi) nm = nt + perturb * xi[si];
+        float xt, tg;
+        noise_mix_target(mode, a, s, x, nm, nt, xt, tg);
         o = f2bf(xt);
         target[si] = tg;
       }
@@ -707,6 +832,31 @@ int az_noise_target(int mode, int batch, int C, int HW, int cpad, const void* la
   az_launch(noise_target_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, mode, batch, C, HW, cpad,
                      (const bf16_t*)latents, (const float*)noise, (const float*)coef_a, (const float*)coef_b,
                      (bf16_t*)noisy_nhwc, (float*)target_f32);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+int az_noise_shape(int batch, int C, int H, int W, void* noise_f32, const void* o, float offset, const void* fields, long nfields,
+                   const void* table, int nlev, void* partials, void* stream) {
+  if (batch <= 0 || batch > 65535 || C <= 0 || H <= 0 || W <= 0 || H > 16384 || W > 16384 || !noise_f32 || nlev < 0 || nlev > 8 ||
+      (nlev && (!fields || !table || nfields <= 0)) || !(offset >= 0.f) || (long)C * H * W >= (1L << 24))
+    return AZ_ERR_ARG(81);
+  const int HW = H * W;
+  int gx = (HW + 255) / 256; if (gx > 64) gx = 64;          // partials: batch * gx pairs
+  az_launch(noise_shape_kernel, dim3(gx, batch), dim3(256), 0, (hipStream_t)stream, C, H, W, (float*)noise_f32, (const float*)o, offset,
+            (const float*)fields, nfields, (const int*)table, nlev, (float*)partials);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+int az_noise_target_ex(int mode, int batch, int C, int HW, int cpad, const void* latents, const void* noise, const void* coef_a,
+                       const void* coef_b, const void* partials, int nblk, const void* xi, float perturb, void* noisy_nhwc,
+                       void* target_f32, void* stream) {
+  if (mode < 0 || mode > 2 || cpad < C || batch <= 0 || C <= 0 || HW <= 0) return AZ_ERR_ARG(82);
+  if (partials && (nblk != ((HW + 255) / 256 > 64 ? 64 : (HW + 255) / 256) || (long)C * HW < 2 || (long)C * HW >= (1L << 24))) return AZ_ERR_ARG(82);
+  if (xi && !(perturb >= 0.f)) return AZ_ERR_ARG(82);
+  long n = (long)batch * HW;
+  az_launch(noise_target_ex_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, mode, batch, C, HW, cpad,
+            (const bf16_t*)latents, (const float*)noise, (const float*)coef_a, (const float*)coef_b, (const float*)partials, nblk,
+            (const float*)xi, perturb, (bf16_t*)noisy_nhwc, (float*)target_f32);
   AZ_CHECK_LAUNCH();
   return AZ_OK;
 }

@@ -646,6 +646,59 @@ def noise_target(mode, latents, noise, coef_a, coef_b, noisy_nhwc, target):
                _ptr(noisy_nhwc), _ptr(target), _stream())
 
 
+def noise_partial_blocks(HW):
+    """Pairs (sum u, sum u^2) per sample that az_noise_shape writes and az_noise_target_ex reads."""
+    return min((int(HW) + 255) // 256, 64)
+
+
+def noise_shape(noise, o, offset, fields, table, levels, partials):
+    """az_noise_shape, in place over noise (B,C,H,W) fp32: + offset * o (o (B,C) fp32 or None) + the weighted bilinear resamplings of
+    the packed level fields.  levels: the host rows (offset, h, w, weight) that `table` (device int32 [n][4], noise.table_tensor) holds
+    -- checked against `fields` here, since the table itself is out of the host's sight; [] / None with fields and table None for no
+    levels.  partials: (B, noise_partial_blocks(H * W), 2) fp32 or None."""
+    _req(noise.dim() == 4 and noise.dtype == F32 and noise.is_contiguous() and noise.is_cuda, "noise_shape noise")
+    B, C, H, W = noise.shape
+    _req(B > 0 and C * H * W < (1 << 24) and float(offset) >= 0.0, "noise_shape sizes")
+    if o is not None:
+        _req(o.dtype == F32 and tuple(o.shape) == (B, C) and o.is_contiguous() and o.device == noise.device, "noise_shape offset draw")
+    levels = list(levels or [])
+    _req(len(levels) <= 8, "noise_shape levels")
+    nfields = 0
+    if levels:
+        _req(fields is not None and table is not None and fields.dtype == F32 and fields.is_contiguous() and fields.device == noise.device and
+             table.dtype == torch.int32 and table.is_contiguous() and table.device == noise.device and table.numel() == 4 * len(levels),
+             "noise_shape level fields / table")
+        nfields = fields.numel()
+        for off, h, w, _ in levels:
+            _req(h >= 1 and w >= 1 and off >= 0 and off + B * C * h * w <= nfields, "noise_shape level geometry")
+    else:
+        _req(fields is None and table is None, "noise_shape: level fields without levels")
+    if partials is not None:
+        _req(partials.dtype == F32 and partials.is_contiguous() and partials.device == noise.device and
+             tuple(partials.shape) == (B, noise_partial_blocks(H * W), 2), "noise_shape partials")
+    lib().call("az_noise_shape", B, C, H, W, _ptr(noise), _ptr(o), float(offset), _ptr(fields), nfields, _ptr(table), len(levels),
+               _ptr(partials), _stream())
+
+
+def noise_target_ex(mode, latents, noise, coef_a, coef_b, partials, xi, perturb, noisy_nhwc, target):
+    """az_noise_target_ex: noise_target with the per-sample normalisation from az_noise_shape's partials (or None) and the input
+    perturbation xi (B,C,H,W) fp32 weighed by perturb (or None)."""
+    B, C, H, W = latents.shape
+    _req(latents.dtype == BF16 and noise.dtype == F32 and latents.is_contiguous() and noise.is_contiguous() and
+         noise.shape == latents.shape and coef_a.dtype == F32 and coef_b.dtype == F32 and coef_a.numel() == B and coef_b.numel() == B and
+         noisy_nhwc.is_contiguous() and tuple(noisy_nhwc.shape[:3]) == (B, H, W) and noisy_nhwc.dtype == BF16 and noisy_nhwc.shape[3] >= C and
+         target.dtype == F32 and target.shape == latents.shape and target.is_contiguous(), "noise_target_ex operands")
+    nblk = 0
+    if partials is not None:
+        nblk = noise_partial_blocks(H * W)
+        _req(partials.dtype == F32 and partials.is_contiguous() and tuple(partials.shape) == (B, nblk, 2) and 2 <= C * H * W < (1 << 24),
+             "noise_target_ex partials")
+    if xi is not None:
+        _req(xi.dtype == F32 and xi.is_contiguous() and xi.shape == latents.shape and float(perturb) >= 0.0, "noise_target_ex perturbation")
+    lib().call("az_noise_target_ex", int(mode), B, C, H * W, noisy_nhwc.shape[3], _ptr(latents), _ptr(noise), _ptr(coef_a), _ptr(coef_b),
+               _ptr(partials), nblk, _ptr(xi), float(perturb) if xi is not None else 0.0, _ptr(noisy_nhwc), _ptr(target), _stream())
+
+
 def mse_loss_fwd_bwd(pred_nhwc, target, w, grad_scale, loss_out, per_sample, dpred):
     B, H, W, ldp = pred_nhwc.shape
     C = target.shape[1]

@@ -1,6 +1,7 @@
 """One micro-step of the reference's hot loop (train.py:2719-2767) on the HIP path.
 
     noise-mix + target (eps / v_prediction / rectified_flow)   train.py:2743-2758  -> az_noise_target
+                                                                (NOISE_MODE offset / pyramid / perturb: az_noise_shape + az_noise_target_ex)
     pred = unet(...)                                            train.py:2760-2761  -> AozoraUNet.forward_nhwc
     loss = weighted_sdxl_mse_loss(pred, target, ts, curve)      train.py:2763       -> az_mse_loss_fwd_bwd
                                                                 (LOSS_TYPE l1 / huber / smooth_l1: az_robust_loss_fwd_bwd)
@@ -22,6 +23,7 @@ import torch
 from . import ops
 from ._lib import lib, AozoraError
 from .loss import loss_widths, parse_loss_type
+from .noise import level_table, parse_noise_mode, table_tensor
 from .schedule import ddpm_coef_tables
 from .unet import AozoraUNet
 from .streams import check as stream_check
@@ -48,12 +50,30 @@ class _Bucket:
         self.dpred8 = torch.zeros(B, H, W, 8, dtype=BF16, device=dev)
         self.loss = torch.zeros(1, dtype=F32, device=dev)
         self.per_sample = torch.zeros(B, dtype=F32, device=dev)
+        # NOISE_MODE buffers (_Bucket.noise_buffers): plain attributes, tensors only under a spec that needs them
+        self.n_o = self.n_fields = self.n_table = self.n_xi = self.n_part = None
+        self.n_levels = []
         self.graph = None
         self.parity = 0
         self.runs = 0
         self.gen = -1          # generation of the activation arena that tape / graph / pred below were made under ...
         self.gen_runs = 0      # ... and the runs since: one allocating run, one recorded or captured run, then replay
         self.pred = None
+
+    def noise_buffers(self, spec):
+        """Static buffers of a NOISE_MODE that draws: o, the packed level fields with their device table, xi, the partial sums."""
+        B, C, H, W = self.lat.shape
+        dev = self.lat.device
+        if spec.offset > 0.0:
+            self.n_o = torch.empty(B, C, dtype=F32, device=dev)
+        if spec.levels:
+            self.n_levels, total = level_table(B, C, H, W, spec)
+            self.n_fields = torch.empty(total, dtype=F32, device=dev)
+            self.n_table = table_tensor(self.n_levels).to(dev)
+        if spec.perturb > 0.0:
+            self.n_xi = torch.empty(B, C, H, W, dtype=F32, device=dev)
+        if spec.normalises:
+            self.n_part = torch.zeros(B, ops.noise_partial_blocks(H * W), 2, dtype=F32, device=dev)
 
     def discard_recorded(self):
         """Everything that holds addresses of the activation arena (it was replaced): rebuilt on the next visits."""
@@ -69,12 +89,15 @@ class _Bucket:
 class TrainStep:
     def __init__(self, unet: AozoraUNet, mode: str = "epsilon", grad_accum: int = 1, world_size: int = 1,
                  loss_curve: Optional[torch.Tensor] = None, use_graph: bool = True, latent_dtype=BF16,
-                 double_buffer: bool = False, loss="MSE"):
+                 double_buffer: bool = False, loss="MSE", noise="normal"):
         if mode not in MODES:
             raise ValueError(f"unknown prediction type {mode!r}")
         # loss: a LOSS_TYPE string or a loss.LossSpec.  Its min-SNR factor is the CALLER's to fold into loss_curve (loss.fold_min_snr,
         # as trainer.train does): nothing here reads it.
         self.loss_spec = parse_loss_type(loss, mode)
+        # noise: a NOISE_MODE string or a noise.NoiseSpec.  A spec that draws (offset, pyramid, perturb) takes its draws per
+        # micro-step (micro_step(noise_aux=noise.draw_aux(...))): like the base noise they are inputs, not device RNG.
+        self.noise_spec = parse_noise_mode(noise)
         self.unet, self.mode, self.ga, self.world = unet, mode, int(grad_accum), int(world_size)
         self.use_graph = use_graph
         self.use_tape = unet.policy.host_tape
@@ -190,10 +213,36 @@ class TrainStep:
         bk.hstage_ev[slot].record(torch.cuda.current_stream())
         return out
 
+    def _check_noise_aux(self, aux, B, C, H, W):
+        """The draws against the spec, before anything is launched: never a silent fall-back to plain noise."""
+        ns = self.noise_spec
+        if not ns.needs_aux:
+            if aux is not None:
+                raise AozoraError(f"noise_aux given, but the step's noise is {ns.describe()!r}, which takes no draws")
+            return
+        if aux is None:
+            raise AozoraError(f"the step's noise is {ns.describe()!r}: micro_step needs noise_aux (noise.draw_aux)")
+
+        def ok(t, shape):
+            return isinstance(t, torch.Tensor) and t.dtype == F32 and tuple(t.shape) == tuple(shape)
+        shapes = [(B, C, h, w) for h, w in ((r.h, r.w) for r in level_table(B, C, H, W, ns)[0])]
+        if ns.offset > 0.0 and not ok(aux.o, (B, C)):
+            raise AozoraError(f"noise_aux.o must be fp32 of shape {(B, C)}")
+        if ns.levels and (aux.z is None or len(aux.z) != len(shapes) or not all(ok(z, s) for z, s in zip(aux.z, shapes))):
+            raise AozoraError(f"noise_aux.z must be fp32 level fields of shapes {shapes}")
+        if ns.perturb > 0.0 and not ok(aux.xi, (B, C, H, W)):
+            raise AozoraError(f"noise_aux.xi must be fp32 of shape {(B, C, H, W)}")
+
     def _launch_sequence(self, bk: _Bucket, after_tail=None):
         u = self.unet
         B, C, H, W = bk.lat.shape
-        ops.noise_target(MODES[self.mode], bk.lat, bk.noise, bk.dev[0], bk.dev[1], bk.x8, bk.target)
+        ns = self.noise_spec
+        if not ns.needs_aux:
+            ops.noise_target(MODES[self.mode], bk.lat, bk.noise, bk.dev[0], bk.dev[1], bk.x8, bk.target)
+        else:
+            if ns.needs_shape:       # (perturb alone adds nothing to the noise itself: no shaping launch)
+                ops.noise_shape(bk.noise, bk.n_o, ns.offset, bk.n_fields, bk.n_table, bk.n_levels, bk.n_part)
+            ops.noise_target_ex(MODES[self.mode], bk.lat, bk.noise, bk.dev[0], bk.dev[1], bk.n_part, bk.n_xi, ns.perturb, bk.x8, bk.target)
         u.begin_step((B, H, W, bk.ctx.shape[1], bk.parity))
         pred = u.forward_nhwc(bk.x8, bk.dev[2], bk.ctx, bk.pooled, bk.tids)
         if self.loss_spec.kind == "mse":
@@ -240,7 +289,7 @@ class TrainStep:
             bk.ntape = NativeTape(bk.tape)           # built here, not at the first replay (one-time ~40 ms of host work)
 
     def micro_step(self, latents, noise, timesteps, embeds, pooled, time_ids, jitter=None, after_tail=None, defer_join=False,
-                   weight_scale=1.0):
+                   weight_scale=1.0, noise_aux=None):
         """latents (B,4,h,w) bf16 ; noise (B,4,h,w) fp32 ; timesteps (B,) int ; embeds (B,L,ctx) ;
         pooled (B,P) ; time_ids (B,6) in the compute dtype (bf16 values).  Returns the device fp32
         scalar holding this micro-step's loss (train.py:2767 reads it with .item()).
@@ -248,11 +297,14 @@ class TrainStep:
         callers whose ranks hold UNEQUAL shares b_r of a ragged global batch GB pass b_r * world / GB, which turns the
         built-in 1/(GA*world) seed into 1/GA * b_r/GB -- each sample then weighs 1/GB as in the single-process run.
         defer_join (needs double_buffer=True): do not wait for this micro-step's parameter-gradient branch; the gradient
-        buffer is complete only after the next micro_step called WITHOUT defer_join (the last one of the window)."""
+        buffer is complete only after the next micro_step called WITHOUT defer_join (the last one of the window).
+        noise_aux: the draws of TrainStep(noise=...) for this micro-step (noise.draw_aux; this rank's rows under data parallel):
+        required by a spec that draws, refused by one that does not."""
         u = self.unet
         B, C, H, W = latents.shape
         L = embeds.shape[1]
         u.check_latent_shape(H, W)
+        self._check_noise_aux(noise_aux, B, C, H, W)
         if defer_join and not self.double_buffer:
             raise AozoraError("defer_join needs TrainStep(double_buffer=True) and the eager executor")
         parity = self._parity if self.double_buffer else 0
@@ -269,6 +321,8 @@ class TrainStep:
                 bk = _Bucket(u.device, B, C, H, W, L, u.cfg.cross_attention_dim, u.cfg.pooled_dim, 5 if self.loss_spec.needs_c else 4)
                 bk.tids = torch.empty(B, 6, dtype=F32, device=u.device)
                 bk.parity = parity
+                if self.noise_spec.needs_aux:
+                    bk.noise_buffers(self.noise_spec)
                 self._buckets[key] = bk
             bk = self._buckets[key]
             if bk.gen != gen:                   # what this bucket recorded points into an arena that is gone
@@ -277,6 +331,13 @@ class TrainStep:
             coef = self._coefficients(bk, timesteps, jitter, time_ids, weight_scale)
             pairs = [(bk.lat, latents.to(BF16)), (bk.noise, noise.to(bk.noise.dtype)), (bk.ctx, embeds.to(BF16)),
                      (bk.pooled, pooled.to(BF16)), (bk.tids, time_ids.float())]
+            if noise_aux is not None:            # at most three more segments: az_stage_inputs takes eight
+                if bk.n_o is not None:
+                    pairs.append((bk.n_o, noise_aux.o))
+                if bk.n_fields is not None:
+                    pairs.append((bk.n_fields, noise_aux.packed()))
+                if bk.n_xi is not None:
+                    pairs.append((bk.n_xi, noise_aux.xi))
             self._stage(self._host_inputs_in_one_copy(bk, pairs), coef, bk.dev)
             if self.use_graph:
                 if after_tail is not None:

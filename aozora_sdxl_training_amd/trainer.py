@@ -23,6 +23,7 @@ from . import data as feed
 from .clip import clip_grad_norm_
 from .ema import EmaWeights, read_options as _ema_options
 from .loss import fold_min_snr, parse_loss_type
+from .noise import draw_aux, parse_noise_mode
 from . import param_groups as pgroups
 from .optimizers import PagedAdamW8bit, RavenAdamW, TitanAdamW
 from .schedule import (CustomCurveLRScheduler, TimestepSampler, ddpm_alphas_cumprod, generate_noise, make_time_ids,
@@ -154,6 +155,9 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     # LOSS_TYPE (loss.parse_loss_type; the reference's GUI offers "MSE" only): read before anything is allocated.  It goes into nothing
     # that is saved: a resumed run reads it from the preset again.
     loss_spec = parse_loss_type(getattr(config, "LOSS_TYPE", "MSE"), mode)
+    # NOISE_MODE (noise.parse_noise_mode; the reference carries "normal" and never reads it): likewise read before the model is loaded,
+    # refused when it cannot be read, and saved nowhere -- its draws depend on (SEED, micro_step) alone (noise.draw_aux).
+    noise_spec = parse_noise_mode(getattr(config, "NOISE_MODE", "normal"))
     config.is_rectified_flow = (mode == "rectified_flow")
     micro_step = optimizer_step = 0
     model_to_load = Path(config.SINGLE_FILE_CHECKPOINT_PATH)
@@ -183,10 +187,12 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     # the step object first: it creates the data-gradient stream, and the order in which a process creates its streams decides
     # which hardware queues they share (streams.py); the optimizer's copy / exchange streams come after it, as in bench.py
     loss_curve = fold_min_snr(timestep_loss_curve_from_config(config, 1000), loss_spec, mode)
-    step = TrainStep(unet, mode=mode, grad_accum=GA, world_size=world, loss_curve=loss_curve, use_graph=False, loss=loss_spec)
+    step = TrainStep(unet, mode=mode, grad_accum=GA, world_size=world, loss_curve=loss_curve, use_graph=False, loss=loss_spec, noise=noise_spec)
     if rank == 0 and (loss_spec.kind != "mse" or loss_spec.min_snr_gamma is not None):
         print(f"INFO: LOSS_TYPE: {loss_spec.describe()}: an option outside the reference; the reported loss is this loss, not the squared error.  "
               "(A LOSS_TYPE this build cannot read used to train MSE without a word and is now refused.)")
+    if rank == 0 and noise_spec.needs_aux:
+        print(f"INFO: NOISE_MODE: {noise_spec.describe()}: an option outside the reference, shaped in HIP between the staged inputs and the UNet forward.")
     from .dist import ShardedRaven, ShardedTitan
     titan = kind == "titan"
     # Single-GPU Titan: the device-accumulator form (dist.ShardedTitan in a group of one: fp32 gradient accumulator in HBM, the same
@@ -365,6 +371,7 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
                 diag = None
                 timesteps, first_ticket = timestep_sampler.sample(GB)
                 noise = generate_noise(batch["latents"], noise_gen, "cpu", step=micro_step, seed=config.SEED)
+                noise_aux = draw_aux(noise_spec, batch["latents"].shape, config.SEED, micro_step)     # None under "normal": nothing drawn
                 jitter = None
                 if config.is_rectified_flow:
                     jitter = torch.rand(timesteps.shape, dtype=torch.float32, generator=seeded_torch_generator("cpu", config.SEED, micro_step, 0x5D1))
@@ -377,6 +384,7 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
                     batch = feed.shard_batch(batch, rank, world, even=False)
                     timesteps, noise = timesteps[rows], noise[rows]
                     jitter = jitter[rows] if jitter is not None else None
+                    noise_aux = noise_aux.rows(rows) if noise_aux is not None else None
                     wscale = (rows.stop - rows.start) * world / GB   # every sample weighs 1/GB, as in the single-process run
                 latents = batch["latents"]
                 B = latents.shape[0]
@@ -393,7 +401,7 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
                     # reached the copy, i.e. until the PREVIOUS micro-step has finished (cProfile: 115 ms per micro-step inside `.to`) -- the
                     # loop then never runs ahead of the GPU and every hiccup of the host idles it
                     loss = step.micro_step(latents, noise, timesteps, batch["embeds"], batch["pooled"], tids, jitter, after_tail=optimizer.reduce_tail if (dp and last and optimizer.overlap) else None,
-                                           weight_scale=wscale)
+                                           weight_scale=wscale, noise_aux=noise_aux)
                     slot = micro_step % RING
                     loss_dev[slot:slot + 1].copy_(loss, non_blocking=True)
                 else:                                            # fewer samples than ranks: this rank sits the micro-step out
@@ -549,6 +557,7 @@ def main(argv=None) -> int:
         return 2
     try:
         parse_loss_type(getattr(config, "LOSS_TYPE", "MSE"), getattr(config, "PREDICTION_TYPE", "epsilon"))
+        noise_spec = parse_noise_mode(getattr(config, "NOISE_MODE", "normal"))
         pgroups.option(config)
     except ValueError as e:
         print(f"ERROR: {e}.")
@@ -583,7 +592,7 @@ def main(argv=None) -> int:
             print("\n" + "=" * 50 + "\n--- RESUMING TRAINING SESSION ---\n")
         else:
             print("\n" + "=" * 50 + f"\n--- STARTING {'RECTIFIED FLOW' if config.is_rectified_flow else 'STANDARD SDXL'} TRAINING ---\n" + "=" * 50 + "\n")
-        print(f"INFO: Noise type: {config.NOISE_MODE}")
+        print(f"INFO: Noise type: {noise_spec.describe()}")
     Path(config.OUTPUT_DIR).mkdir(parents=True, exist_ok=True)
     # --unet-config FILE (JSON of unet_spec.UNetConfig fields): a UNet geometry other than SDXL-base (the test suite's
     # reduced-width model); the GUI never passes it

@@ -321,6 +321,27 @@ int az_nhwc_to_nchw(int batch, int C, int HW, int ldsrc, const void* src, void* 
 /* ref: train.py:2743-2758 (rectified-flow mix / scheduler.add_noise / get_velocity) */
 int az_noise_target(int mode, int batch, int C, int HW, int cpad, const void* latents, const void* noise,
                     const void* coef_a, const void* coef_b, void* noisy_nhwc, void* target_f32, void* stream);
+/* Noise modes (NOISE_MODE; an option outside the reference, not in the reference's loop): noise offset, multi-resolution
+ * ("pyramid") noise and input perturbation, between the staged inputs and az_noise_target's arithmetic.
+ * az_noise_shape writes, in place over the fp32 noise NCHW [B][C][H][W],
+ *     u = eps + offset * o[b][c] + sum_{l=1..nlev} weight_l * up_l(z_l)[b][c][y][x]
+ * o fp32 [B][C] (null: no offset term); fields: the level fields z_l packed in one fp32 buffer of nfields floats, level l at
+ * table[4l] as [B][C][h_l][w_l]; table: DEVICE int32 [nlev][4] = (offset, h_l, w_l, bits of the fp32 weight_l).  up_l: bilinear
+ * resampling to (H, W), half-pixel centres (F.interpolate(mode="bilinear", align_corners=False)), taps and fractions from the
+ * integer numerator (2y+1) h_l - H.  Plain fp32 operations, no contraction.  partials (null: none): fp32 [B][nblk][2], nblk =
+ * min(ceil(H W / 256), 64), the sums (u, u^2) of each block of a sample in a fixed order (no atomics; independent of B).
+ * Refused: nlev outside 0..8, a null fields / table with nlev > 0, offset < 0 or NaN, C H W >= 2^24. */
+/* ref: train.py:2743 (the noise handed to the mix; the reference has the plain draw only) */
+int az_noise_shape(int batch, int C, int H, int W, void* noise_f32, const void* o, float offset, const void* fields, long nfields,
+                   const void* table, int nlev, void* partials, void* stream);
+/* az_noise_target with two optional inputs.  partials + nblk (az_noise_shape's): the noise is first normalised per sample,
+ * eps' = u * r_b, r_b = 1 / sqrt((S2 - S1 (S1 / n)) / (n - 1)), n = C HW, S1 / S2 the sample's partials summed in block order
+ * (unbiased std about the sample's mean; correctly rounded / and sqrt).  xi fp32 NCHW + perturb: the noisy latents are mixed from
+ * eps' + perturb * xi while the target is built from eps'.  Both null: az_noise_target bit for bit. */
+/* ref: train.py:2743-2758 (as az_noise_target) */
+int az_noise_target_ex(int mode, int batch, int C, int HW, int cpad, const void* latents, const void* noise, const void* coef_a,
+                       const void* coef_b, const void* partials, int nblk, const void* xi, float perturb, void* noisy_nhwc,
+                       void* target_f32, void* stream);
 /* weighted_sdxl_mse_loss (train.py:2408-2416) forward + d(loss*scale)/dpred.
  * pred NHWC bf16 [B][HW][ldp], target fp32 NCHW, w fp32 [B] (curve[timestep]).  loss_out fp32[1]
  * is overwritten; scratch_f32 >= 64*B floats (ordered partial sums, no atomics).  dpred NHWC bf16 padded to cpad channels (zeros). */
