@@ -1,5 +1,5 @@
 """The training loop around the HIP step (train.py:2544-2830 restated on this package's objects): data feed -> micro-step
-(TrainStep: noise mix, UNet forward, weighted MSE, backward) -> clip -> Raven / Titan / 8-bit AdamW -> LR curve -> reporter ->
+(TrainStep: noise mix, UNet forward, weighted MSE, backward) -> clip -> Raven / Titan / 8-bit AdamW / Prodigy -> LR curve -> reporter ->
 checkpoints / resume.  It is the caller of the hot path (SURVEY.md 8a row a1 with the 8f rows plugged in); no GUI, no
 offline caching -- `config` is any object with the reference's flat attribute names (config.TrainingConfig builds one from
 a GUI preset: `python -m aozora_sdxl_training_amd.trainer --config X.json`, see main()).
@@ -25,7 +25,7 @@ from .ema import EmaWeights, read_options as _ema_options
 from .loss import fold_min_snr, parse_loss_type
 from .noise import draw_aux, parse_noise_mode
 from . import param_groups as pgroups
-from .optimizers import PagedAdamW8bit, RavenAdamW, TitanAdamW
+from .optimizers import PagedAdamW8bit, Prodigy, RavenAdamW, TitanAdamW
 from .schedule import (CustomCurveLRScheduler, TimestepSampler, ddpm_alphas_cumprod, generate_noise, make_time_ids,
                        seeded_torch_generator, timestep_loss_curve_from_config, trainable_mask)
 from .telemetry import Reporter
@@ -42,6 +42,17 @@ _MASTER_SR_REFUSAL = ("master_weights and stochastic_rounding do not combine: st
 _MASTER_HOST_TITAN_REFUSAL = ("master_weights does not combine with TITAN_HOST_GRADIENTS = true: that path runs the drop-in "
                               "optimizers.TitanAdamW (fp32 gradients in pinned host memory), which keeps no master copy -- drop one of the two")
 _ADAMW8_DP_REFUSAL = "paged_adamw_8bit runs at one rank only: data-parallel training supports raven and titan"
+_PRODIGY_DP_REFUSAL = ("prodigy runs at one rank only: its step size is estimated from two sums over ALL trainable elements, which the "
+                       "data-parallel shards do not exchange -- data-parallel training supports raven and titan")
+_PRODIGY_SR_REFUSAL = ("stochastic_rounding is an option of raven and titan (RAVEN_PARAMS / TITAN_PARAMS): prodigy always keeps an fp32 "
+                       "master copy, of which the bf16 parameters are the round-to-nearest image -- remove the key from PRODIGY_PARAMS")
+_PRODIGY_MASTER_REFUSAL = ("master_weights is an option of raven and titan (RAVEN_PARAMS / TITAN_PARAMS): prodigy always keeps an fp32 "
+                           "master copy, there is nothing to switch -- remove the key from PRODIGY_PARAMS")
+_PRODIGY_GROUPS_REFUSAL = ("param_groups is an option of raven, titan and paged_adamw_8bit: prodigy estimates ONE step size over all "
+                           "trainable elements and takes one group -- remove the key from PRODIGY_PARAMS")
+_PRODIGY_KEYS = ("betas", "beta3", "eps", "weight_decay", "use_bias_correction", "safeguard_warmup", "d0", "d_coef", "growth_rate",
+                 "ema_decay", "ema_warmup")
+_PARAMS_KEY = {"titan": "TITAN_PARAMS", "paged_adamw_8bit": "PAGED_ADAMW_8BIT_PARAMS", "prodigy": "PRODIGY_PARAMS"}
 
 
 def _momentum_dtype(v):
@@ -97,6 +108,8 @@ def _master_option(config) -> bool:
         if "master_weights" in dict(getattr(config, "PAGED_ADAMW_8BIT_PARAMS", {}) or {}):
             raise ValueError(_MASTER_8BIT_REFUSAL)
         return False
+    if kind == "prodigy":           # its own master copy, always (prodigy_options refuses the key)
+        return False
     hp = dict(getattr(config, "TITAN_PARAMS" if kind == "titan" else "RAVEN_PARAMS", {}) or {})
     if not _as_bool(hp.get("master_weights", False)):
         return False
@@ -128,6 +141,38 @@ def _optimizer_8bit(config, params, groups=None):
     return PagedAdamW8bit(params, lr=lr, betas=tuple(hp["betas"]), eps=hp["eps"], weight_decay=hp["weight_decay"], min_8bit_size=4096)
 
 
+def prodigy_options(config, world: int = 1) -> dict:
+    """PRODIGY_PARAMS (config.py: `<mode>_prodigy_params` of the preset's active block, default {}) -> the keywords of
+    optimizers.Prodigy, lr excepted (that is max(curve), as for the other optimizers).  Refuses, before anything is allocated: more than
+    one rank, the options of the flat optimizers that have no meaning here, an unknown key (a typo must not silently train the default),
+    eps <= 0, d0 <= 0, betas outside [0, 1).  Absent keys take the optimizer's defaults (INTEGRATION.md "The Prodigy optimizer")."""
+    from .optimizers.prodigy import check_options
+    if world > 1:
+        raise ValueError(_PRODIGY_DP_REFUSAL)
+    hp = dict(getattr(config, "PRODIGY_PARAMS", None) or {})
+    for key, why in (("stochastic_rounding", _PRODIGY_SR_REFUSAL), ("master_weights", _PRODIGY_MASTER_REFUSAL), ("param_groups", _PRODIGY_GROUPS_REFUSAL)):
+        if key in hp:
+            raise ValueError(why)
+    unknown = sorted(k for k in hp if k not in _PRODIGY_KEYS)
+    if unknown:
+        raise ValueError(f"PRODIGY_PARAMS holds unknown key(s) {unknown}: this build reads {sorted(_PRODIGY_KEYS)} (the learning rate comes "
+                         "from LR_CUSTOM_CURVE)")
+    kw = {k: hp[k] for k in _PRODIGY_KEYS[:9] if k in hp and hp[k] is not None}
+    try:
+        for k in ("eps", "weight_decay", "d0", "d_coef", "growth_rate", "beta3"):
+            if k in kw:
+                kw[k] = float(kw[k])
+        if "betas" in kw:
+            kw["betas"] = tuple(float(b) for b in kw["betas"])
+    except (TypeError, ValueError):
+        raise ValueError(f"PRODIGY_PARAMS: a numeric option cannot be read as a number: {hp}") from None
+    for k in ("use_bias_correction", "safeguard_warmup"):
+        if k in kw:
+            kw[k] = _as_bool(kw[k])
+    check_options(kw.get("betas", (0.9, 0.999)), kw.get("beta3"), kw.get("eps", 1e-8), kw.get("d0", 1e-6))
+    return kw
+
+
 def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = None, num_workers: Optional[int] = None):
     """Run config.MAX_TRAIN_STEPS micro-steps.  Returns dict(losses, grad_norms, lrs, micro_step, optimizer_step, saved).
 
@@ -142,14 +187,18 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     eightbit = kind == "paged_adamw_8bit"
     if eightbit and dp:
         raise ValueError(_ADAMW8_DP_REFUSAL)
+    # OPTIMIZER_TYPE "prodigy" (optimizers.Prodigy; not in the reference): its options are read, and what it does not combine with
+    # refused, before anything is allocated
+    prodigy = kind == "prodigy"
+    prodigy_kw = prodigy_options(config, world) if prodigy else None
     # "ema_decay" [, "ema_warmup"] in the ACTIVE optimizer's dictionary: an fp32 EMA of the trainable weights (ema.py; not in the
     # reference, absent = off).  Read first: an invalid value is refused before anything is allocated.
-    ema_decay, ema_warmup = _ema_options(getattr(config, {"titan": "TITAN_PARAMS", "paged_adamw_8bit": "PAGED_ADAMW_8BIT_PARAMS"}.get(kind, "RAVEN_PARAMS"), None))
+    ema_decay, ema_warmup = _ema_options(getattr(config, _PARAMS_KEY.get(kind, "RAVEN_PARAMS"), None))
     master = _master_option(config)          # "master_weights" (not in the reference, absent = off); refusals before anything is allocated
     # "param_groups" in the active optimizer's dictionary (param_groups.py; not in the reference's trainer, absent or [] = off): the rules
     # are read, and what they do not combine with refused, before anything is allocated.  Like LOSS_TYPE they go into nothing that is
     # saved: a resumed run reads them from the preset again.
-    group_rules = pgroups.option(config)
+    group_rules = [] if prodigy else pgroups.option(config)
     GA = int(config.GRADIENT_ACCUMULATION_STEPS)
     mode = getattr(config, "PREDICTION_TYPE", "epsilon")
     # LOSS_TYPE (loss.parse_loss_type; the reference's GUI offers "MSE" only): read before anything is allocated.  It goes into nothing
@@ -204,6 +253,18 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     if eightbit:
         # one rank, the module-optimizer branch of the loop: expose_grads -> clip_grad_norm_ -> step (blockwise 8-bit AdamW in HIP)
         optimizer = _optimizer_8bit(config, params, groups)
+    elif prodigy:
+        # likewise: expose_grads -> clip_grad_norm_ -> step (two fused passes and two scalar kernels in HIP, d never leaves the device)
+        curve0 = getattr(config, "LR_CUSTOM_CURVE", [])
+        lr0 = max(p_[1] for p_ in curve0) if curve0 else config.LEARNING_RATE
+        optimizer = Prodigy(params, lr=lr0, **prodigy_kw)
+        if rank == 0:
+            shown = {k: v for k, v in optimizer.param_groups[0].items() if k not in ("params", "lr")}
+            print(f"INFO: OPTIMIZER_TYPE prodigy is ON ({shown}; {optimizer.state_bytes} bytes of fp32 state: master, starting point, m, v, s): "
+                  "an optimizer outside the reference; its step size d is estimated on the device, the learning rate multiplies it")
+            if lr0 < 1e-2:
+                print(f"INFO: prodigy: the largest learning rate of LR_CUSTOM_CURVE is {lr0:g}.  Prodigy's learning rate is a MULTIPLIER of its own "
+                      "step-size estimate and belongs near 1 (a warm-up to 1.0 and a decay); the reference's AdamW-scale curve of 8e-7 would train nothing")
     elif not host_titan:
         # The flat fused optimizer (one rank: no collectives): m / v resident in HBM (or, RAVEN_STATE_ON_HOST, prefetched under the
         # window's last micro-step and written back under the next window), update of the whole flat range in one launch per
@@ -288,6 +349,8 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     hist = dict(losses=[], grad_norms=[], lrs=[], saved=[])
     if ema is not None:
         hist["saved_ema"] = []
+    if prodigy:
+        hist["prodigy_d"] = []
     # emergency-save flag: the GUI writes PROJECT_ROOT/force_save.flag and runs the trainer with cwd = PROJECT_ROOT
     # (gui.py:5947, 5983; train.py:2550 looks next to itself) -> default = the process' working directory
     flag = Path(getattr(config, "FORCE_SAVE_FLAG", None) or Path.cwd() / "force_save.flag")
@@ -448,6 +511,8 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
                         ema.update()                              # same stream, right behind the step
                     optimizer.zero_grad(set_to_none=True)
                     optimizer_step += 1
+                    if prodigy:                     # (this branch has already blocked on the norm's .item())
+                        hist["prodigy_d"].append(optimizer.d_value())
                     if not gc_frozen:           # the launch tapes / pools built during the first window are permanent: keep the cyclic
                         gc.collect()            # collector from walking them (tens of thousands of objects) in the middle of later windows
                         gc.freeze()
@@ -469,7 +534,7 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
                     if (every > 0 and optimizer_step % every == 0) or forced:            # train.py:2805-2815
                         reason = "Emergency checkpoint requested" if forced and not (every > 0 and optimizer_step % every == 0) else "Saving checkpoint"
                         flush()                                  # the progress lines of this window come before the checkpoint's (log order of the reference)
-                        reporter.log_message(f"\n--- {reason} at optimizer step {optimizer_step} ---")
+                        reporter.log_message(f"\n--- {reason} at optimizer step {optimizer_step} ---" + (f" (prodigy d = {optimizer.d_value():.6e})" if prodigy else ""))
                         mname, sname = ckpt.checkpoint_names(stem, optimizer_step)
                         if hasattr(optimizer, "synchronize_params"):
                             optimizer.synchronize_params()      # updates / all-gathers still running under the next forward's slots must have landed
@@ -544,7 +609,7 @@ def main(argv=None) -> int:
     (gui.py:5930-5975), here for the native step.  One process per GPU: started by torch.distributed.run (RANK / WORLD_SIZE /
     LOCAL_RANK in the environment) the ranks form an RCCL group and config.BATCH_SIZE is the GLOBAL micro-batch.
     Out of scope, refused with a message instead of being attempted: the Anima DiT mode, offline VAE / text-encoder caching
-    (the cache must exist), fp16 mixed precision and paged_adamw_8bit under data parallel."""
+    (the cache must exist), fp16 mixed precision and paged_adamw_8bit or prodigy under data parallel."""
     import os
     import sys
     from .config import TrainingConfig
@@ -558,11 +623,14 @@ def main(argv=None) -> int:
     try:
         parse_loss_type(getattr(config, "LOSS_TYPE", "MSE"), getattr(config, "PREDICTION_TYPE", "epsilon"))
         noise_spec = parse_noise_mode(getattr(config, "NOISE_MODE", "normal"))
-        pgroups.option(config)
+        if str(config.OPTIMIZER_TYPE).lower() == "prodigy":
+            prodigy_options(config, int(os.environ.get("WORLD_SIZE", "1")))
+        else:
+            pgroups.option(config)
     except ValueError as e:
         print(f"ERROR: {e}.")
         return 2
-    if str(config.OPTIMIZER_TYPE).lower() not in ("raven", "titan", "paged_adamw_8bit"):
+    if str(config.OPTIMIZER_TYPE).lower() not in ("raven", "titan", "paged_adamw_8bit", "prodigy"):
         raise ValueError(f"Unsupported optimizer type: '{config.OPTIMIZER_TYPE}'")          # train.py:2290
     if str(config.OPTIMIZER_TYPE).lower() == "paged_adamw_8bit" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         print(f"ERROR: {_ADAMW8_DP_REFUSAL}.")

@@ -476,6 +476,54 @@ int az_titan_offload(long n, const void* g, void* g_host_f32, void* staging_f32,
 /* ref: train.py:2271-2288 (create_optimizer: bnb.optim.PagedAdamW8bit) */
 int az_adamw8bit_step(int ntensors, const void* desc, long nblocks, const void* hyper, const void* qmaps, const void* coef,
                       void* stream);
+/* Prodigy (arXiv 2306.06101; an optimizer the reference does not have -- INTEGRATION.md "The Prodigy optimizer" states the arithmetic in
+ * full, tests/prodigy_ref.py restates it on the CPU): AdamW-shaped moments scaled by a step size d that the device estimates itself
+ * from two sums over all trainable elements, with an fp32 master copy w of the bf16 parameters.  One step is az_prodigy_begin, one
+ * az_prodigy_moments per contiguous range, az_prodigy_finish, one az_prodigy_apply per range, all on ONE stream: 2 R + 2 launches for
+ * R ranges, no copy to the host, no synchronisation; every sum has a fixed order (no floating-point atomics), so a step is
+ * bit-reproducible.  Shared buffers:
+ *   dstate (device fp64[8], 8-byte aligned): d, d_max, d_numerator, d_denom, d_hat, k, d0, one spare word.  The caller initialises
+ *     d = d_max = d0 > 0 and the rest to 0.
+ *   hyper (HOST fp64[16], 8-byte aligned, read DURING az_prodigy_begin -- the values travel in the kernel's arguments, the caller may
+ *     reuse the array at once): lr, beta1, beta2, beta3, eps, weight_decay, d_coef, growth_rate (+inf = none), use_bias_correction
+ *     (0 / 1), safeguard_warmup (0 / 1); the rest unused.  The caller issues no step when lr == 0.
+ *   consts (device, 128 bytes, 8-byte aligned): fp32[16] = c_m, c_v, c_s, beta1, beta2, beta3 (written by begin), dlr, wd_dlr, eps_d
+ *     (written by finish), weight_decay != 0, skip (1 from begin until finish has found d_denom != 0); then fp64[8] carried from begin
+ *     to finish.  Every fp32 constant is computed in fp64 on the device and rounded once.
+ *   partials (device fp64 pairs, 8-byte aligned): az_prodigy_moments over n elements writes az_prodigy_partials(n) pairs (numerator
+ *     sum, denominator sum), one per block, at the pointer it is given; the caller lays the slices of a step's launches back to back
+ *     and passes the total to az_prodigy_finish.
+ * az_prodigy_partials(n): that pair count for the current device (blocks of 256 threads, 8 elements per thread and iteration, at most
+ *   8 blocks per CU, a grid-stride loop beyond); 0 for n == 0; n < 0 or no device are errors (negative).
+ * az_prodigy_begin: bc = sqrt(1 - beta2^(k+1)) / (1 - beta1^(k+1)) or 1; dlr = d lr bc; c_m = d (1 - beta1); c_v = d d (1 - beta2);
+ *   c_s = (d / d0) dlr, or (d / d0) d with safeguard_warmup.  A null or misaligned pointer is an argument error.
+ * az_prodigy_moments, element i in [0, n): gr = g[i] * coef[0] (coef: device fp32[1] or null = 1; a bf16 gradient is rounded to bf16
+ *   after the multiplication); m = fma(gr, c_m, m beta1); v = v beta2 + ((c_v gr) gr); s = fma(gr, c_s, s beta3); the sums take
+ *   (double)gr * (double)(p0 - w) -- the difference rounded to fp32, the product exact -- and (double)|s|, accumulated in fp64 per
+ *   thread, then per block.  w, p0 fp32 (read), g bf16 (gdtype 0) or fp32 (1), m / v / s fp32 in place.  16-byte accesses from the
+ *   first element at which w, p0, g, m, v and s are all 16-byte aligned, element-wise before it, in the tail, and everywhere when the
+ *   six cannot be co-aligned.  n == 0 returns 0 without a launch (and writes no pair); n < 0, a null w / p0 / g / m / v / s / consts /
+ *   partials, gdtype out of range or a pointer not aligned to its element are argument errors.
+ * az_prodigy_finish: sums npartials pairs in a fixed order; d_numerator = beta3 d_numerator + (d / d0) dlr * sum; d_denom = sum.  If
+ *   d_denom == 0 the step ends there: skip stays 1, d / d_max / d_hat / k are unchanged.  Otherwise d_hat = d_coef d_numerator /
+ *   d_denom; d = max(d, d_hat) while d == d0; d_max = max(d_max, d_hat); d = min(d_max, d growth_rate); k += 1; dlr (the OLD d),
+ *   wd_dlr = weight_decay dlr and eps_d = d_new eps for the apply pass.  npartials == 0 is a step with d_denom == 0; npartials < 0, a
+ *   null dstate / consts, null partials with npartials > 0 or a misaligned pointer are argument errors.
+ * az_prodigy_apply, element i in [0, n), nothing when skip is set: w = fma(w, -wd_dlr, w) when weight_decay != 0; w = w + ((-dlr m) /
+ *   (sqrtf(v) + eps_d)); p = bf16(w), round to nearest even.  p bf16 (written, never read), w fp32 in place, m / v fp32 (read).
+ *   16-byte accesses where p, w, m and v are co-aligned, as above.  n == 0 returns 0 without a launch; n < 0, a null pointer or one not
+ *   aligned to its element are argument errors.  NaN and inf follow IEEE rules throughout. */
+/* ref: not in the reference; stands where optimizer.step() does, train.py:2783 */
+long az_prodigy_partials(long n);
+/* ref: not in the reference; stands where optimizer.step() does, train.py:2783 */
+int az_prodigy_begin(const void* dstate, const void* hyper_host, void* consts, void* stream);
+/* ref: not in the reference; stands where optimizer.step() does, train.py:2783 */
+int az_prodigy_moments(long n, const void* w, const void* p0, const void* g, int gdtype, void* m, void* v, void* s, const void* consts,
+                       const void* coef, void* partials, void* stream);
+/* ref: not in the reference; stands where optimizer.step() does, train.py:2783 */
+int az_prodigy_finish(long npartials, const void* partials, void* dstate, void* consts, void* stream);
+/* ref: not in the reference; stands where optimizer.step() does, train.py:2783 */
+int az_prodigy_apply(long n, void* p, void* w, const void* m, const void* v, const void* consts, void* stream);
 
 /* ---- native launch tape: the executor seam (SURVEY.md 8b "az_unet_step") ----------------------------------------------------
  * The step's launch sequence is static (same entry points, pointers, streams and events every step of a resolution bucket).  The
