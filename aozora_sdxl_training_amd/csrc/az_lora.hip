@@ -1,0 +1,291 @@
+// LoRA adapter products (include/aozora_hip.h az_lora_*): three shapes of product with one tiny dimension, each on
+// v_mfma_f32_16x16x32_bf16 with the small dimension padded to 16 (or 32 as the k-depth) by zero FRAGMENTS -- never in memory.
+//   down  : OUT[M][r]   = s X[M][K] . W[r][K]^T          one pass over X; a block's 4 waves split the k-range, fixed-order sum
+//   up    : Y[M][N]    += s U[M][r] . W[N][r]^T          read-modify-write of Y, k-depth r
+//   wgrad : OUT[ns][nb] (+)= s S[M][ns]^T . G[M][nb]     sum over M: fp32 partials per row range, then a fixed-order second stage
+// All three use the operand order of az_gemm.hip (D^T = small-frag x big-frag), so a lane owns 4 consecutive output columns.
+// Operand maps of the MFMA: lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15], j = 0..7; the result
+// D[row = 4 (l >> 4) + i][col = l & 15], i = 0..3.  No floating-point atomics anywhere: every sum has a fixed order.
+#include "az_common.h"
+#include "aozora_hip.h"
+
+namespace {
+
+__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+
+// elements k .. k + 7 of a row of kdim (a multiple of 4) elements that is only 8-byte aligned; zeros from kdim on and when !ok
+__device__ __forceinline__ bf16x8 load_small8(const bf16_t* row, int k, int kdim, bool ok) {
+  bf16x4 lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
+  if (ok && k < kdim) lo = *(const bf16x4*)(row + k);
+  if (ok && k + 4 < kdim) hi = *(const bf16x4*)(row + k + 4);
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+__device__ __forceinline__ bf16x4 pack4(f32x4 v) {
+  bf16x4 o;
+  o[0] = (short)f2bf(v[0]); o[1] = (short)f2bf(v[1]); o[2] = (short)f2bf(v[2]); o[3] = (short)f2bf(v[3]);
+  return o;
+}
+
+// ---- down: OUT[m][p r + n] = bf16(s sum_k X[m][p xps + k] W_p[n][k]) ---------------------------------------------------------------
+// A block owns 16 rows of X and all r outputs of part blockIdx.y (NT tiles of 16).  Its 4 waves deal the k-range among themselves in
+// groups of KU 32-deep steps (the loads of a group are issued together: the product is bound by the latency of its one pass over X,
+// and a grid of M / 16 blocks keeps 4 waves per row tile in flight); wave 0 adds the other three partial sums in wave order.
+template <int NT, int KU>
+__global__ __launch_bounds__(256) void lora_down_kernel(int M, int K, int r, float s, const bf16_t* __restrict__ X, long ldx, long xps,
+                                                        const bf16_t* __restrict__ W, long ldw, long wps, bf16_t* __restrict__ U, long ldu) {
+  __shared__ f32x4 red[3][NT][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, p = blockIdx.y;
+  const long m0 = (long)blockIdx.x * 16;
+  const int li = lane & 15, kq = (lane >> 4) * 8;
+  const long m = m0 + li;
+  const bool mok = m < M;
+  const bf16_t* xrow = X + (mok ? m : 0) * ldx + (long)p * xps;
+  const bf16_t* wp = W + (long)p * wps;
+  const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  f32x4 acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k0 = wave * 32 * KU; k0 < K; k0 += 4 * 32 * KU) {
+    bf16x8 xf[KU], wf[KU][NT];
+#pragma unroll
+    for (int u = 0; u < KU; ++u) {
+      const int k = k0 + 32 * u + kq;
+      const bool kok = k < K;                     // K % 8 == 0: an 8-chunk is inside or outside as a whole
+      xf[u] = zero8;
+      if (mok && kok) xf[u] = *(const bf16x8*)(xrow + k);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int n = t * 16 + li;
+        wf[u][t] = zero8;
+        if (kok && n < r) wf[u][t] = *(const bf16x8*)(wp + (long)n * ldw + k);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < KU; ++u) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) acc[t] = mfma16(wf[u][t], xf[u], acc[t]);
+    }
+  }
+  if (wave) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) red[wave - 1][t][lane] = acc[t];
+  }
+  __syncthreads();
+  if (wave || !mok) return;
+  bf16_t* urow = U + m * ldu + (long)p * r;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int n4 = t * 16 + (lane >> 4) * 4;
+    const f32x4 v = ((acc[t] + red[0][t][lane]) + red[1][t][lane]) + red[2][t][lane];
+    if (n4 < r) *(bf16x4*)(urow + n4) = pack4(v * s);
+  }
+}
+
+// ---- up: Y[m][p yps + n] = bf16(float(Y) + s sum_{k < r} U[m][p ups + k] W_p[n][k]) -------------------------------------------------
+// A wave owns 16 rows and 128 columns of part blockIdx.z; its U fragments (KS k-steps of 32) are loaded once.
+template <int KS>
+__global__ __launch_bounds__(256) void lora_up_kernel(int M, int N, int r, float s, const bf16_t* __restrict__ U, long ldu, long ups,
+                                                      const bf16_t* __restrict__ W, long ldw, long wps, bf16_t* Y, long ldy, long yps) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, p = blockIdx.z;
+  const long m0 = ((long)blockIdx.y * 4 + wave) * 16;
+  if (m0 >= M) return;
+  const int li = lane & 15, kq = (lane >> 4) * 8;
+  const long m = m0 + li;
+  const bool mok = m < M;
+  const bf16_t* urow = U + (mok ? m : 0) * ldu + (long)p * ups;
+  bf16x8 uf[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) uf[ks] = load_small8(urow, ks * 32 + kq, r, mok);
+  const bf16_t* wp = W + (long)p * wps;
+  bf16_t* yrow = Y + (mok ? m : 0) * ldy + (long)p * yps;
+  const int nbeg = blockIdx.x * 128, nend = min(N, nbeg + 128);
+  for (int n0 = nbeg; n0 < nend; n0 += 16) {
+    const int nw = n0 + li;
+    const bool wok = nw < N;
+    const bf16_t* wrow = wp + (long)(wok ? nw : 0) * ldw;
+    const int n4 = n0 + (lane >> 4) * 4;
+    const bool yok = mok && n4 < N;               // N % 4 == 0: a 4-group is inside or outside as a whole
+    bf16x4 y = {0, 0, 0, 0};
+    if (yok) y = *(const bf16x4*)(yrow + n4);     // issued with the W loads: one latency per tile, not two
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) acc = mfma16(load_small8(wrow, ks * 32 + kq, r, wok), uf[ks], acc);
+    if (yok) {
+      f32x4 o;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o[i] = bf2f((bf16_t)y[i]) + s * acc[i];
+      *(bf16x4*)(yrow + n4) = pack4(o);
+    }
+  }
+}
+
+// ---- wgrad, stage 1: P[p][split][i_s][i_b] = sum over the split's rows of S[m][p sps + i_s] G[m][p gps + i_b] (fp32) -----------------
+// A block owns 64 columns of G (16 per wave), all ns columns of S (NT tiles of 16) and rows [split rps, min(M, (split + 1) rps)).
+// Both operands are k-strided in memory (k = the row), so each 32-row slice goes through LDS transposed: T[column][40] with the 32
+// rows contiguous (80-byte row stride: 16-byte aligned fragment reads).  One buffer, two barriers per slice.
+constexpr int LKP = 40;
+template <int NT>
+__global__ __launch_bounds__(256) void lora_wgrad_partial_kernel(int M, int ns, int nb, int rps, const bf16_t* __restrict__ S, long ld_s, long sps,
+                                                                 const bf16_t* __restrict__ G, long ld_g, long gps, float* __restrict__ P) {
+  __shared__ __attribute__((aligned(16))) bf16_t St[NT * 16 * LKP];
+  __shared__ __attribute__((aligned(16))) bf16_t Gt[64 * LKP];
+  constexpr int SQ = NT * 4;                       // 4-element groups per row of the S slice (padded to NT * 16 columns)
+  constexpr int SI = (32 * SQ + 255) / 256;        // ... per thread
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int split = blockIdx.y, nsplit = gridDim.y, p = blockIdx.z;
+  const int b0 = blockIdx.x * 64;
+  const long mbeg = (long)split * rps, mend = min((long)M, mbeg + rps);
+  const int li = lane & 15, kq = (lane >> 4) * 8;
+  const bf16_t* Sp = S + (long)p * sps;
+  const bf16_t* Gp = G + (long)p * gps;
+  const int grow = tid >> 3, gcol = (tid & 7) * 8;
+  f32x4 acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  bf16x8 gv;
+  bf16x4 sv[SI];
+  // the global loads of a slice are issued one slice ahead (registers), so they fly under the previous slice's LDS round and MFMAs
+  auto load_slice = [&](long mk) {
+    gv = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    if (mk + grow < mend && b0 + gcol < nb) gv = *(const bf16x8*)(Gp + (mk + grow) * ld_g + b0 + gcol);      // nb % 8 == 0
+#pragma unroll
+    for (int i = 0; i < SI; ++i) {
+      const int it = tid + i * 256, row = it / SQ, c4 = (it % SQ) * 4;
+      sv[i] = bf16x4{0, 0, 0, 0};
+      if (it < 32 * SQ && mk + row < mend && c4 < ns) sv[i] = *(const bf16x4*)(Sp + (mk + row) * ld_s + c4);  // ns % 4 == 0
+    }
+  };
+  load_slice(mbeg);
+  for (long mk = mbeg; mk < mend; mk += 32) {
+    __syncthreads();                               // the previous slice's fragments have been read
+#pragma unroll
+    for (int j = 0; j < 8; ++j) Gt[(gcol + j) * LKP + grow] = (bf16_t)gv[j];
+#pragma unroll
+    for (int i = 0; i < SI; ++i) {
+      const int it = tid + i * 256, row = it / SQ, c4 = (it % SQ) * 4;
+      if (it < 32 * SQ) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) St[(c4 + j) * LKP + row] = (bf16_t)sv[i][j];
+      }
+    }
+    __syncthreads();
+    if (mk + 32 < mend) load_slice(mk + 32);
+    const bf16x8 gf = *(const bf16x8*)(Gt + (wave * 16 + li) * LKP + kq);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = mfma16(*(const bf16x8*)(St + (t * 16 + li) * LKP + kq), gf, acc[t]);
+  }
+  const int ib = b0 + wave * 16 + li;
+  if (ib >= nb) return;
+  float* Pp = P + ((long)p * nsplit + split) * ns * nb;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int is = t * 16 + (lane >> 4) * 4 + i;
+      if (is < ns) Pp[(long)is * nb + ib] = acc[t][i];
+    }
+  }
+}
+
+// ---- wgrad, stage 2: out(p, i_s, i_b) = bf16((accumulate ? float(out) : 0) + s sum_split P[p][split][i_s][i_b]), splits ascending -----
+__global__ __launch_bounds__(256) void lora_wgrad_finish_kernel(int ns, int nb, int parts, int nsplit, float s, const float* __restrict__ P,
+                                                                bf16_t* out, long os_s, long os_b, long ops, int accumulate) {
+  const long per = (long)ns * nb, i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= per * parts) return;
+  const int p = (int)(i / per);
+  const long e = i - (long)p * per;
+  const int is = (int)(e / nb), ib = (int)(e - (long)is * nb);
+  const float* src = P + (long)p * nsplit * per + e;
+  float sum = 0.f;
+  for (int k = 0; k < nsplit; ++k) sum += src[(long)k * per];
+  bf16_t* o = out + (long)p * ops + (long)is * os_s + (long)ib * os_b;
+  float v = s * sum;
+  if (accumulate) v = bf2f(*o) + v;
+  *o = f2bf(v);
+}
+
+inline bool al(const void* p, int a) { return ((uintptr_t)p & (uintptr_t)(a - 1)) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int az_lora_down_bf16(int M, int K, int r, int parts, float s, const void* X, long ldx, long x_part_stride, const void* W, long ldw,
+                      long w_part_stride, void* out, long ldo, void* stream) {
+  if (M <= 0 || K <= 0 || (K & 7) || r < 4 || (r & 3) || parts < 1 || parts > 3 || (long)parts * r > 192) return AZ_ERR_ARG(110);
+  if (!X || !W || !out || !al(X, 16) || !al(W, 16) || !al(out, 8)) return AZ_ERR_ARG(111);
+  if ((ldx & 7) || (ldw & 7) || (ldo & 3) || (x_part_stride & 7) || (w_part_stride & 7) || x_part_stride < 0 || w_part_stride < 0 ||
+      ldx < (parts - 1) * x_part_stride + K || ldw < K || ldo < (long)parts * r)
+    return AZ_ERR_ARG(112);
+  const dim3 grid((unsigned)((M + 15) / 16), (unsigned)parts), block(256);
+  const bf16_t *x = (const bf16_t*)X, *w = (const bf16_t*)W;
+  bf16_t* u = (bf16_t*)out;
+  hipStream_t st = (hipStream_t)stream;
+  if (r <= 16) az_launch(lora_down_kernel<1, 4>, grid, block, 0, st, M, K, r, s, x, ldx, x_part_stride, w, ldw, w_part_stride, u, ldo);
+  else if (r <= 32) az_launch(lora_down_kernel<2, 4>, grid, block, 0, st, M, K, r, s, x, ldx, x_part_stride, w, ldw, w_part_stride, u, ldo);
+  else if (r <= 64) az_launch(lora_down_kernel<4, 2>, grid, block, 0, st, M, K, r, s, x, ldx, x_part_stride, w, ldw, w_part_stride, u, ldo);
+  else az_launch(lora_down_kernel<12, 1>, grid, block, 0, st, M, K, r, s, x, ldx, x_part_stride, w, ldw, w_part_stride, u, ldo);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+
+int az_lora_up_bf16(int M, int N, int r, int parts, float s, const void* U, long ldu, long u_part_stride, const void* W, long ldw,
+                    long w_part_stride, void* Y, long ldy, long y_part_stride, void* stream) {
+  if (M <= 0 || N <= 0 || (N & 3) || r < 4 || (r & 3) || r > 192 || parts < 1 || parts > 3) return AZ_ERR_ARG(113);
+  if (!U || !W || !Y || !al(U, 8) || !al(W, 8) || !al(Y, 8)) return AZ_ERR_ARG(114);
+  if ((ldu & 3) || (ldw & 3) || (ldy & 3) || (u_part_stride & 3) || (w_part_stride & 3) || (y_part_stride & 3) || u_part_stride < 0 ||
+      w_part_stride < 0 || y_part_stride < 0 || ldu < (parts - 1) * u_part_stride + r || ldw < r || ldy < (parts - 1) * y_part_stride + N ||
+      (parts > 1 && y_part_stride < N))
+    return AZ_ERR_ARG(115);
+  const long gy = ((long)M + 63) / 64;
+  if (gy > 65535) return AZ_ERR_ARG(115);
+  const dim3 grid((unsigned)((N + 127) / 128), (unsigned)gy, (unsigned)parts), block(256);
+  const bf16_t *u = (const bf16_t*)U, *w = (const bf16_t*)W;
+  bf16_t* y = (bf16_t*)Y;
+  hipStream_t st = (hipStream_t)stream;
+  if (r <= 32) az_launch(lora_up_kernel<1>, grid, block, 0, st, M, N, r, s, u, ldu, u_part_stride, w, ldw, w_part_stride, y, ldy, y_part_stride);
+  else if (r <= 64) az_launch(lora_up_kernel<2>, grid, block, 0, st, M, N, r, s, u, ldu, u_part_stride, w, ldw, w_part_stride, y, ldy, y_part_stride);
+  else az_launch(lora_up_kernel<6>, grid, block, 0, st, M, N, r, s, u, ldu, u_part_stride, w, ldw, w_part_stride, y, ldy, y_part_stride);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+
+int az_lora_wgrad_bf16(int M, int ns, int nb, int parts, float s, const void* S, long ld_s, long s_part_stride, const void* G, long ld_g,
+                       long g_part_stride, void* out, long out_stride_s, long out_stride_b, long out_part_stride, int accumulate,
+                       void* workspace, long workspace_bytes, void* stream) {
+  if (M <= 0 || ns < 4 || (ns & 3) || ns > 192 || nb <= 0 || (nb & 7) || parts < 1 || parts > 3) return AZ_ERR_ARG(116);
+  if (!S || !G || !out || !workspace || !al(S, 8) || !al(G, 16) || !al(out, 2) || !al(workspace, 4)) return AZ_ERR_ARG(117);
+  if ((ld_s & 3) || (ld_g & 7) || (s_part_stride & 3) || (g_part_stride & 7) || s_part_stride < 0 || g_part_stride < 0 ||
+      ld_s < (parts - 1) * s_part_stride + ns || ld_g < (parts - 1) * g_part_stride + nb || out_stride_s <= 0 || out_stride_b <= 0 ||
+      out_part_stride < 0)
+    return AZ_ERR_ARG(118);
+  // rows per split: about 512 workgroups in all, at most 64 splits, whole 32-row slices, and partials that fit the workspace
+  const long per = (long)parts * ns * nb * 4;
+  long cap = workspace_bytes / per;
+  if (cap < 1) return AZ_ERR_ARG(119);
+  const long base = (((long)nb + 63) / 64) * parts;
+  long want = (512 + base - 1) / base;
+  if (want > 64) want = 64;
+  if (want > cap) want = cap;
+  const long slices = ((long)M + 31) / 32;
+  if (want > slices) want = slices;
+  const long rps = ((slices + want - 1) / want) * 32;
+  const int nsplit = (int)(((long)M + rps - 1) / rps);
+  const dim3 grid((unsigned)((nb + 63) / 64), (unsigned)nsplit, (unsigned)parts), block(256);
+  const bf16_t *sp = (const bf16_t*)S, *gp = (const bf16_t*)G;
+  float* P = (float*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  if (ns <= 16) az_launch(lora_wgrad_partial_kernel<1>, grid, block, 0, st, M, ns, nb, (int)rps, sp, ld_s, s_part_stride, gp, ld_g, g_part_stride, P);
+  else if (ns <= 32) az_launch(lora_wgrad_partial_kernel<2>, grid, block, 0, st, M, ns, nb, (int)rps, sp, ld_s, s_part_stride, gp, ld_g, g_part_stride, P);
+  else if (ns <= 64) az_launch(lora_wgrad_partial_kernel<4>, grid, block, 0, st, M, ns, nb, (int)rps, sp, ld_s, s_part_stride, gp, ld_g, g_part_stride, P);
+  else az_launch(lora_wgrad_partial_kernel<12>, grid, block, 0, st, M, ns, nb, (int)rps, sp, ld_s, s_part_stride, gp, ld_g, g_part_stride, P);
+  AZ_CHECK_LAUNCH();
+  const long total = (long)parts * ns * nb;
+  az_launch(lora_wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ns, nb, parts, nsplit, s, (const float*)P, (bf16_t*)out,
+            out_stride_s, out_stride_b, out_part_stride, accumulate);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,146 @@
+"""LoRA training (INTEGRATION.md "LoRA"; not in the reference, whose train.py is full fine-tuning only): the options of
+`LORA_PARAMS`, the adapter file in the kohya-ss layout that ComfyUI and A1111 load, the merged model, and the loader.  Host-side
+logic only; the arithmetic is az_lora_* (csrc/az_lora.hip) inside AozoraUNet.linear."""
+from __future__ import annotations
+
+import json
+from pathlib import Path
+from typing import Dict, Optional, Tuple
+
+import torch
+
+from . import checkpoint as ckpt
+from .unet_spec import LORA_RANKS, LoraSpec, lora_modules
+
+_KEYS = ("rank", "alpha", "targets", "save_merged")
+DP_REFUSAL = ("LORA_PARAMS under data parallel (more than one rank): the flat gradient exchange would move the whole frozen base's "
+              "gradient (5 GB at SDXL size) for a few MB of adapters; run LoRA on one GPU")
+EMA_REFUSAL = "LORA_PARAMS with \"ema_decay\": the EMA's file writer knows only the full model (EMA of adapters is a follow-up)"
+
+
+def _as_bool(v) -> bool:
+    return v.strip().lower() in ("true", "1", "t", "y", "yes") if isinstance(v, str) else bool(v)
+
+
+def options(config, world: int = 1, ema_decay=None, cfg=None) -> Tuple[Optional[LoraSpec], bool]:
+    """config.LORA_PARAMS -> (LoraSpec or None, save_merged).  Absent or {} = off.  Everything that cannot be read or combined is
+    refused here (ValueError), before a UNet is loaded."""
+    hp = getattr(config, "LORA_PARAMS", None)
+    if not hp:
+        return None, False
+    if not isinstance(hp, dict):
+        raise ValueError(f"LORA_PARAMS must be a dictionary, got {type(hp).__name__}")
+    unknown = sorted(k for k in hp if k not in _KEYS)
+    if unknown:
+        raise ValueError(f"LORA_PARAMS holds unknown key(s) {unknown}: this build reads {list(_KEYS)}")
+    rank = hp.get("rank", 16)
+    if isinstance(rank, (list, tuple, dict)):
+        raise ValueError(f"LORA_PARAMS: one rank for all adapters, got {rank!r} (more than one rank is a follow-up)")
+    try:
+        rank_i, alpha = int(rank), float(hp.get("alpha", rank))
+        if rank_i != float(rank):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"LORA_PARAMS: rank / alpha cannot be read as numbers: {hp}") from None
+    if rank_i not in LORA_RANKS:
+        raise ValueError(f"LORA_PARAMS: rank {rank_i} is not one of {list(LORA_RANKS)}")
+    if not alpha > 0.0:
+        raise ValueError(f"LORA_PARAMS: alpha must be > 0, got {alpha}")
+    targets = hp.get("targets", "") or ""
+    if isinstance(targets, (list, tuple)):
+        targets = ", ".join(str(t) for t in targets)
+    if world > 1:
+        raise ValueError(DP_REFUSAL)
+    if ema_decay is not None:
+        raise ValueError(EMA_REFUSAL)
+    spec = LoraSpec(rank_i, alpha, str(targets))
+    from .unet_spec import SDXL_BASE
+    lora_modules(cfg if cfg is not None else SDXL_BASE, spec)        # a target that selects nothing / something out of scope
+    return spec, _as_bool(hp.get("save_merged", False))
+
+
+# ---------------- the adapter file ---------------------------------------------------------------------------------------------------
+def file_key(module: str) -> str:
+    """`lora_unet_<single-file module path with . -> _>`: the module path is checkpoint._sd_name's (the 1680-name pin covers it)."""
+    return "lora_unet_" + ckpt._sd_name(module + ".weight")[:-len(".weight")].replace(".", "_")
+
+
+def file_tensors(lora_state: Dict[str, torch.Tensor], spec: LoraSpec) -> Dict[str, torch.Tensor]:
+    out = {}
+    for name, t in lora_state.items():
+        module, _, leaf = name.rpartition(".lora_")
+        key = file_key(module)
+        out[key + (".lora_down.weight" if leaf == "A.weight" else ".lora_up.weight")] = t.detach().to("cpu", torch.bfloat16).contiguous()
+        out[key + ".alpha"] = torch.tensor(float(spec.alpha), dtype=torch.bfloat16)
+    return out
+
+
+def file_metadata(spec: LoraSpec) -> Dict[str, str]:
+    return {"ss_network_module": "networks.lora", "ss_network_dim": str(spec.rank), "ss_network_alpha": f"{float(spec.alpha):g}",
+            "ss_base_model_version": "sdxl_base_v1-0"}
+
+
+def save_lora_file(path, unet, spec: Optional[LoraSpec] = None):
+    """Write ONLY the adapters: <key>.lora_down.weight [r][in], .lora_up.weight [out][r], .alpha (0-dim), bf16."""
+    from safetensors.torch import save_file
+    spec = spec if spec is not None else unet.lora
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    save_file(file_tensors(unet.lora_state_dict(), spec), str(path), metadata=file_metadata(spec))
+    return path
+
+
+def read_lora_file(path, unet) -> Dict[str, torch.Tensor]:
+    """-> {<module>.lora_A.weight / .lora_B.weight: tensor} for unet.load_lora_state_dict; the file must hold exactly this UNet's
+    adapters at its rank and alpha."""
+    from safetensors import safe_open
+    spec = unet.lora
+    out = {}
+    with safe_open(str(path), framework="pt", device="cpu") as f:
+        keys = set(f.keys())
+        meta = f.metadata() or {}
+        if meta.get("ss_network_dim") not in (None, str(spec.rank)):
+            raise ValueError(f"{Path(path).name} holds rank {meta.get('ss_network_dim')} adapters; LORA_PARAMS asks for rank {spec.rank}")
+        want = set()
+        for name in unet.lora_state_dict():
+            module, _, leaf = name.rpartition(".lora_")
+            k = file_key(module) + (".lora_down.weight" if leaf == "A.weight" else ".lora_up.weight")
+            want.update((k, file_key(module) + ".alpha"))
+            if k not in keys:
+                raise KeyError(f"{k} is missing from {Path(path).name}")
+            out[name] = f.get_tensor(k)
+            a = float(f.get_tensor(file_key(module) + ".alpha"))
+            if a != float(torch.tensor(float(spec.alpha), dtype=torch.bfloat16)):
+                raise ValueError(f"{Path(path).name}: alpha {a} of {module} differs from LORA_PARAMS' {spec.alpha}")
+        if keys != want:
+            raise KeyError(f"{Path(path).name} holds adapters this LoraSpec does not: {sorted(keys - want)[:3]}")
+    return out
+
+
+def merged_state(unet) -> Dict[str, torch.Tensor]:
+    """The base state dict with W + s B A in place of every adapted weight: formed in fp32 on the CPU, rounded once (by save_model)."""
+    sd = {k: v.detach().cpu() for k, v in unet.state_dict().items()}
+    ls = {k: v.detach().float().cpu() for k, v in unet.lora_state_dict().items()}
+    s = unet.lora.scale
+    for name, A in ls.items():
+        if name.endswith(".lora_A.weight"):
+            module = name[:-len(".lora_A.weight")]
+            sd[module + ".weight"] = sd[module + ".weight"].float() + s * (ls[module + ".lora_B.weight"] @ A)
+    return sd
+
+
+def load_unet(base_path, device, cfg, spec: LoraSpec, seed: int, adapters_path=None):
+    """The base out of a single-file checkpoint into AozoraUNet(lora=spec); adapters from `adapters_path` (resume) or freshly drawn."""
+    from .unet import AozoraUNet
+    from .unet_spec import SDXL_BASE
+    cfg = cfg if cfg is not None else SDXL_BASE
+    cin, cout = ckpt.peek_channels(base_path)
+    if (cin, cout) != (cfg.in_channels, cfg.out_channels):
+        raise ValueError(f"checkpoint has in/out channels {cin}/{cout}; this build runs {cfg.in_channels}/{cfg.out_channels}")
+    unet = AozoraUNet(cfg, device, lora=spec)
+    unet.load_state_dict(ckpt.read_unet_state(base_path, list(unet.state_dict())))
+    if adapters_path is not None:
+        unet.load_lora_state_dict(read_lora_file(adapters_path, unet))
+    else:
+        unet.init_lora(seed)
+    return unet

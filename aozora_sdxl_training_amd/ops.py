@@ -332,6 +332,68 @@ def conv_wgrad(dy, x, dw, *, stride=1, cout_real=None, accumulate=True, split_k=
 
 
 # ---------------------------------------------------------------------------------------------
+# LoRA adapter products (az_lora_*)
+# ---------------------------------------------------------------------------------------------
+
+def _lora_parts(total, parts, what):
+    _req(1 <= parts <= 3 and total % parts == 0, f"{what}: {total} rows / columns do not split into {parts} parts")
+    return total // parts
+
+
+def lora_down(x, w, out, *, parts=1, scale=1.0):
+    """out[:, p r:(p+1) r] = scale * x_p @ w_p^T (az_lora_down_bf16).  w [parts * r][K] (the parts stacked by rows), out [M][parts * r].
+    x [M][K] is shared by the parts (parts must then be 1: a stacked w is one product of rank parts * r), or x [M][parts * K] holds one
+    column slice per part (du = s dy B: x = dy of a fused projection, w = the stacked B^T copies)."""
+    M, xc, ldx = _rows(x)
+    wr, K, ldw = _rows(w)
+    om, oc, ldo = _rows(out)
+    r = _lora_parts(wr, parts, "lora_down w")
+    _req(xc == parts * K and (om, oc) == (M, parts * r), f"lora_down shapes x {tuple(x.shape)} w {tuple(w.shape)} out {tuple(out.shape)}")
+    _req(K % 8 == 0 and r % 4 == 0 and 4 <= r and parts * r <= 192, f"lora_down: K {K} % 8, rank {r} % 4, parts * rank <= 192")
+    _req(ldx % 8 == 0 and ldw % 8 == 0 and ldo % 4 == 0 and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0 and out.data_ptr() % 8 == 0,
+         "lora_down: operand alignment")
+    with _prof("lora_down" + (f" {M}x{parts}x{r}x{K}" if PROFILE_SHAPES else ""), 2.0 * M * parts * r * K, 2.0 * (M * parts * K + parts * r * K + M * parts * r)):
+        lib().call("az_lora_down_bf16", M, K, r, parts, float(scale), _ptr(x), ldx, K, _ptr(w), ldw, r * ldw, _ptr(out), ldo, _stream())
+    return out
+
+
+def lora_up(u, w, y, *, parts=1, scale=1.0):
+    """y[:, p N:(p+1) N] += scale * u[:, p r:(p+1) r] @ w_p^T in place (az_lora_up_bf16).  u [M][parts * r], w [parts * N][r] (the
+    parts stacked by rows), y [M][parts * N] -- the column slices of a fused output."""
+    M, uc, ldu = _rows(u)
+    wr, r, ldw = _rows(w)
+    ym, yc, ldy = _rows(y)
+    N = _lora_parts(wr, parts, "lora_up w")
+    _req(uc == parts * r and (ym, yc) == (M, parts * N), f"lora_up shapes u {tuple(u.shape)} w {tuple(w.shape)} y {tuple(y.shape)}")
+    _req(N % 4 == 0 and r % 4 == 0 and 4 <= r <= 192, f"lora_up: N {N} % 4, rank {r} % 4 and <= 192")
+    _req(ldu % 4 == 0 and ldw % 4 == 0 and ldy % 4 == 0 and u.data_ptr() % 8 == 0 and w.data_ptr() % 8 == 0 and y.data_ptr() % 8 == 0,
+         "lora_up: operand alignment")
+    with _prof("lora_up" + (f" {M}x{parts}x{N}x{r}" if PROFILE_SHAPES else ""), 2.0 * M * parts * N * r, 2.0 * (2 * M * parts * N + parts * N * r + M * parts * r)):
+        lib().call("az_lora_up_bf16", M, N, r, parts, float(scale), _ptr(u), ldu, r, _ptr(w), ldw, N * ldw, _ptr(y), ldy, N, _stream())
+    return y
+
+
+def lora_wgrad(small, big, out, *, parts=1, scale=1.0, accumulate=True, small_major=True):
+    """out (+)= scale * small_p^T @ big_p, summed over the rows (az_lora_wgrad_bf16).  small [M][parts * ns] (du or u), big [M][parts * nb]
+    (x or dy).  small_major: out [parts * ns][nb] (dA_cat = du^T x); else out [parts * nb][ns] (the stacked dB_p = s dy_p^T u_p)."""
+    M, sc, ld_s = _rows(small)
+    Mb, bc, ld_g = _rows(big)
+    orows, ocols, ldo = _rows(out)
+    ns, nb = _lora_parts(sc, parts, "lora_wgrad small"), _lora_parts(bc, parts, "lora_wgrad big")
+    _req(Mb == M and (orows, ocols) == ((parts * ns, nb) if small_major else (parts * nb, ns)),
+         f"lora_wgrad shapes small {tuple(small.shape)} big {tuple(big.shape)} out {tuple(out.shape)}")
+    _req(ns % 4 == 0 and 4 <= ns <= 192 and nb % 8 == 0, f"lora_wgrad: small width {ns} % 4 and <= 192, big width {nb} % 8")
+    _req(ld_s % 4 == 0 and ld_g % 8 == 0 and small.data_ptr() % 8 == 0 and big.data_ptr() % 16 == 0, "lora_wgrad: operand alignment")
+    ws = workspace(out.device)
+    ws_bytes = ws.splitk.numel() * 4 - (16 << 10)            # the last 16 KiB are the GEMM core's arrival counters
+    os_s, os_b, ops_ = (ldo, 1, ns * ldo) if small_major else (1, ldo, nb * ldo)
+    with _prof("lora_wgrad" + (f" {parts}x{ns}x{nb}x{M}" if PROFILE_SHAPES else ""), 2.0 * M * parts * ns * nb, 2.0 * (M * parts * (ns + nb) + 2 * parts * ns * nb)):
+        lib().call("az_lora_wgrad_bf16", M, ns, nb, parts, float(scale), _ptr(small), ld_s, ns, _ptr(big), ld_g, nb, _ptr(out), os_s, os_b, ops_,
+                   int(accumulate), _ptr(ws.splitk), ws_bytes, _stream())
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # attention
 # ---------------------------------------------------------------------------------------------
 

@@ -20,6 +20,7 @@ import torch
 
 from . import checkpoint as ckpt
 from . import data as feed
+from . import lora as lora_mod
 from .clip import clip_grad_norm_
 from .ema import EmaWeights, read_options as _ema_options
 from .loss import fold_min_snr, parse_loss_type
@@ -194,6 +195,12 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     # "ema_decay" [, "ema_warmup"] in the ACTIVE optimizer's dictionary: an fp32 EMA of the trainable weights (ema.py; not in the
     # reference, absent = off).  Read first: an invalid value is refused before anything is allocated.
     ema_decay, ema_warmup = _ema_options(getattr(config, _PARAMS_KEY.get(kind, "RAVEN_PARAMS"), None))
+    # LORA_PARAMS (lora.options; not in the reference, absent or {} = off): rank-r adapters on the attention projections, the base frozen.
+    # Read, and what it does not combine with refused, before a UNet is loaded.
+    lora_spec, lora_merged = lora_mod.options(config, world, ema_decay, unet.cfg if unet is not None else None)
+    if unet is not None and getattr(unet, "lora", None) != lora_spec:
+        raise ValueError(f"the UNet passed in was built with lora={getattr(unet, 'lora', None)!r} but LORA_PARAMS gives {lora_spec!r}: "
+                         "build it with the matching spec (lora.load_unet)")
     master = _master_option(config)          # "master_weights" (not in the reference, absent = off); refusals before anything is allocated
     # "param_groups" in the active optimizer's dictionary (param_groups.py; not in the reference's trainer, absent or [] = off): the rules
     # are read, and what they do not combine with refused, before anything is allocated.  Like LOSS_TYPE they go into nothing that is
@@ -211,22 +218,35 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     micro_step = optimizer_step = 0
     model_to_load = Path(config.SINGLE_FILE_CHECKPOINT_PATH)
     sampler_seed, optimizer_state, ts_state = config.SEED, None, None
-    ema_saved = master_saved = None
+    ema_saved = master_saved = lora_resume = None
     if getattr(config, "RESUME_TRAINING", False):                                   # train.py:2558-2573
         rs = ckpt.load_training_state(config.RESUME_STATE_PATH, GA)
         micro_step, optimizer_step = rs["micro_step"], rs["optimizer_step"]
         sampler_seed, ts_state, optimizer_state = rs["sampler_seed"], rs["timestep_sampler_state"], rs["optimizer_state"]
-        model_to_load = Path(config.RESUME_MODEL_PATH)
+        if lora_spec is None:
+            model_to_load = Path(config.RESUME_MODEL_PATH)
+        else:       # RESUME_MODEL_PATH holds the adapters alone; the base comes from (and saves merge into) SINGLE_FILE_CHECKPOINT_PATH
+            lora_resume = Path(config.RESUME_MODEL_PATH)
         ema_saved, master_saved = rs["raw"].get("ema_state"), rs["raw"].get("master_state")
         ckpt.restore_rng(rs["raw"])
     if unet is None:
-        unet = ckpt.load_unet(model_to_load, device)
+        unet = (ckpt.load_unet(model_to_load, device) if lora_spec is None else
+                lora_mod.load_unet(model_to_load, device, None, lora_spec, config.SEED, lora_resume))
     names = [n for n, _ in unet.named_parameters()]
     excl = getattr(config, "UNET_EXCLUDE_TARGETS", []) or []
     if isinstance(excl, str):                                                        # "a, b" -> ["a", "b"] (train.py:304-307)
         excl = [k.strip() for k in excl.split(",") if k.strip()]
-    for (n, p), m in zip(unet.named_parameters(), trainable_mask(names, [k for k in excl if k])):
-        p.requires_grad = m                                                          # train.py:2664-2667
+    if lora_spec is not None:        # the whole base frozen, every adapter trainable: one contiguous range of the flat buffers
+        for n, p in unet.named_parameters():
+            p.requires_grad = ".lora_" in n
+        if rank == 0:
+            n_ad = sum(p.numel() for n, p in unet.named_parameters() if ".lora_" in n)
+            print(f"INFO: LoRA is ON (rank {lora_spec.rank}, alpha {lora_spec.alpha:g}, {len(unet.lora_state_dict()) // 2} adapted projections, {n_ad} "
+                  f"trainable elements{', merged model saved too' if lora_merged else ''}): an option outside the reference; the base is frozen, "
+                  "UNET_EXCLUDE_TARGETS is not applied, and every model file holds the adapters alone (kohya-ss layout)")
+    else:
+        for (n, p), m in zip(unet.named_parameters(), trainable_mask(names, [k for k in excl if k])):
+            p.requires_grad = m                                                      # train.py:2664-2667
     params = [p for p in unet.parameters() if p.requires_grad]
     # the rules against the trainable parameters (a rule that matches none is refused: a typo must not silently train the default)
     groups = None
@@ -409,6 +429,15 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
             resolve(rec)
             reporter.log_step(rec["micro_step"], timing_data=rec["timing"], diag_data=None)
 
+    def write_model(path):
+        """A model file of this run: the merged single-file checkpoint, or -- LoRA -- the adapters alone (+ `<stem>_merged` on request)."""
+        if lora_spec is None:
+            ckpt.save_model(path, unet, model_to_load, torch.bfloat16)
+            return
+        lora_mod.save_lora_file(path, unet, lora_spec)
+        if lora_merged:
+            ckpt.save_model(Path(path).with_name(Path(path).stem + "_merged.safetensors"), lora_mod.merged_state(unet), model_to_load, torch.bfloat16)
+
     done = False
     gc_frozen = False
     # The loop's CPU tensor work is a handful of tiny ops per micro-step (noise draw, time ids, collate).  With torch's default of one
@@ -547,7 +576,7 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
                             Path(config.OUTPUT_DIR).mkdir(parents=True, exist_ok=True)
                             torch.save({**optimizer.save_cpu_state(), **(ema_extra or {})}, str(Path(config.OUTPUT_DIR) / sname) + f".rank{rank}")
                         if rank == 0:
-                            ckpt.save_model(Path(config.OUTPUT_DIR) / mname, unet, model_to_load, torch.bfloat16)
+                            write_model(Path(config.OUTPUT_DIR) / mname)
                             if ema is not None:
                                 ckpt.save_model(Path(config.OUTPUT_DIR) / ckpt.ema_names(stem, optimizer_step), ema_sd, model_to_load, torch.bfloat16)
                             ckpt.save_training_state(Path(config.OUTPUT_DIR) / sname, optimizer_step, micro_step,
@@ -580,7 +609,7 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
         optimizer.synchronize_params()           # the last step's overlapped update / all-gather must have landed
     ema_sd = ema.state_dict() if ema is not None else None       # (every rank: the gather is a collective)
     if rank == 0:
-        ckpt.save_model(final, unet, model_to_load, torch.bfloat16)
+        write_model(final)
         if ema is not None:
             ckpt.save_model(Path(config.OUTPUT_DIR) / ckpt.ema_names(stem), ema_sd, model_to_load, torch.bfloat16)
         print("All tasks complete. Final model saved.")
@@ -604,6 +633,22 @@ def set_seed(seed):
     print(f"INFO: Set random seed to {seed}")
 
 
+def _model_config(argv):
+    """--unet-config FILE (JSON of unet_spec.UNetConfig fields): a UNet geometry other than SDXL-base (the test suite's
+    reduced-width model); the GUI never passes it.  -> UNetConfig or None"""
+    import argparse
+    import json
+    ap = argparse.ArgumentParser(add_help=False)
+    ap.add_argument("--unet-config", default=None)
+    path = ap.parse_known_args(None if argv is None else list(argv))[0].unet_config
+    if not path:
+        return None
+    from .unet_spec import UNetConfig
+    with open(path) as f:
+        fields = json.load(f)
+    return UNetConfig(**{k: (tuple(v) if isinstance(v, list) else v) for k, v in fields.items()})
+
+
 def main(argv=None) -> int:
     """Process entry: `python -m aozora_sdxl_training_amd.trainer --config X.json` -- what the GUI spawns for train.py
     (gui.py:5930-5975), here for the native step.  One process per GPU: started by torch.distributed.run (RANK / WORLD_SIZE /
@@ -623,6 +668,8 @@ def main(argv=None) -> int:
     try:
         parse_loss_type(getattr(config, "LOSS_TYPE", "MSE"), getattr(config, "PREDICTION_TYPE", "epsilon"))
         noise_spec = parse_noise_mode(getattr(config, "NOISE_MODE", "normal"))
+        model_cfg = _model_config(argv)     # --unet-config: the geometry LoRA targets are judged against (None = SDXL-base)
+        lora_spec = lora_mod.options(config, int(os.environ.get("WORLD_SIZE", "1")), cfg=model_cfg)[0]
         if str(config.OPTIMIZER_TYPE).lower() == "prodigy":
             prodigy_options(config, int(os.environ.get("WORLD_SIZE", "1")))
         else:
@@ -662,21 +709,14 @@ def main(argv=None) -> int:
             print("\n" + "=" * 50 + f"\n--- STARTING {'RECTIFIED FLOW' if config.is_rectified_flow else 'STANDARD SDXL'} TRAINING ---\n" + "=" * 50 + "\n")
         print(f"INFO: Noise type: {noise_spec.describe()}")
     Path(config.OUTPUT_DIR).mkdir(parents=True, exist_ok=True)
-    # --unet-config FILE (JSON of unet_spec.UNetConfig fields): a UNet geometry other than SDXL-base (the test suite's
-    # reduced-width model); the GUI never passes it
-    import argparse
-    import json
-    ap = argparse.ArgumentParser(add_help=False)
-    ap.add_argument("--unet-config", default=None)
-    spec = ap.parse_known_args(None if argv is None else list(argv))[0].unet_config
     unet = None
-    if spec:
-        from .unet_spec import UNetConfig
-        with open(spec) as f:
-            fields = json.load(f)
-        model_cfg = UNetConfig(**{k: (tuple(v) if isinstance(v, list) else v) for k, v in fields.items()})
+    if model_cfg is not None:
         src = config.RESUME_MODEL_PATH if config.RESUME_TRAINING else config.SINGLE_FILE_CHECKPOINT_PATH
-        unet = ckpt.load_unet(src, device, model_cfg)
+        if lora_spec is None:
+            unet = ckpt.load_unet(src, device, model_cfg)
+        else:
+            unet = lora_mod.load_unet(config.SINGLE_FILE_CHECKPOINT_PATH, device, model_cfg, lora_spec, config.SEED,
+                                      config.RESUME_MODEL_PATH if config.RESUME_TRAINING else None)
     try:
         train(config, unet=unet, device=device)
     except pgroups.GroupsError as e:         # a rule that matches no trainable parameter is only known once the model is loaded

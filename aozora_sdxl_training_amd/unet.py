@@ -27,7 +27,7 @@ import torch
 
 from . import ops
 from ._lib import lib, AozoraError, ForkEvent, Record, Wait, Live
-from .unet_spec import UNetConfig, SDXL_BASE, param_table, up_resnet_channels
+from .unet_spec import UNetConfig, SDXL_BASE, param_table, up_resnet_channels, LoraSpec, lora_table
 
 @dataclass
 class ExecPolicy:
@@ -207,7 +207,7 @@ class _UNetCall(torch.autograd.Function):
 
 
 class AozoraUNet:
-    def __init__(self, cfg: UNetConfig = SDXL_BASE, device="cuda:0", policy: Optional[ExecPolicy] = None):
+    def __init__(self, cfg: UNetConfig = SDXL_BASE, device="cuda:0", policy: Optional[ExecPolicy] = None, lora: Optional[LoraSpec] = None):
         if not torch.cuda.is_available():
             raise AozoraError("AozoraUNet needs a HIP device; there is no CPU fallback")
         self.cfg = cfg
@@ -224,7 +224,12 @@ class AozoraUNet:
             raise AozoraError("az_init failed")
         lib()._fn["az_make_current"](self._ctx)
         self.training = True
-        self._table = param_table(cfg)
+        # LoRA (INTEGRATION.md "LoRA"): the adapters are ordinary entries of the flat buffers BEHIND conv_out.bias -- the base slots keep
+        # their offsets -- and the base table stays what state_dict / load_state_dict mean
+        self.lora = lora
+        self._base_table = param_table(cfg)
+        self._table = self._base_table + (lora_table(cfg, lora) if lora is not None else [])
+        self._lora_groups: Dict[tuple, object] = {}
         self._layout()
         self._pools: Dict[tuple, _Pool] = {}
         self._pool: Optional[_Pool] = None
@@ -331,7 +336,7 @@ class AozoraUNet:
         skip = set()
         for name in names:
             o, st, shape = self._slots[name]
-            if not name.endswith(".weight") or name in skip:
+            if not name.endswith(".weight") or name in skip or ".lora_" in name:
                 continue
             if len(st) == 2:
                 rows, cols = st
@@ -346,6 +351,23 @@ class AozoraUNet:
                 rows *= 2
                 skip.add(name.replace("to_k", "to_v"))
             self._wt_jobs.append((o, rows, cols))
+        # adapters: the backward data products of az_lora_* are NT products over transposed copies -- the adjacent down matrices of a
+        # fused group as ONE stacked [parts r][K] -> [K][parts r] job (dx += du A_cat), every up matrix [N][r] -> [r][N] on its own
+        # (stacked they are the [parts r][N] operand of du = s dy B)
+        ltab = self._table[len(self._base_table):]
+        i = 0
+        while i < len(ltab):
+            o, st, _ = self._slots[ltab[i][0]]
+            if math.prod(st) % ALIGN:
+                raise AozoraError(f"adapter {ltab[i][0]} {st} does not fill whole {ALIGN}-element slots: stacked groups would not be adjacent")
+            n = 1
+            if ltab[i][0].endswith(".lora_A.weight"):
+                while i + n < len(ltab) and ltab[i + n][0].endswith(".lora_A.weight") and self._slots[ltab[i + n][0]][1] == st:
+                    n += 1
+                if n > 3:
+                    raise AozoraError(f"{n} adjacent down matrices from {ltab[i][0]} on: a fused group has at most 3 parts")
+            self._wt_jobs.append((o, n * st[0], st[1]))
+            i += n
         # 3x3 conv weights [Cout][9][Cin] -> W'[Cin][9][Cout] (nine strided transposes) for the NT-form conv dgrad
         self._wt_conv_jobs: List[Tuple[int, int, int]] = []   # (offset, Cout, Cin)
         for name in names:
@@ -549,12 +571,136 @@ class AozoraUNet:
             yield self._params[name]
 
     def state_dict(self):
+        """The BASE model's tensors (adapters: lora_state_dict)."""
         self.wait_tail_params()
-        return {name: self._params[name].detach() for name, _ in self._table}
+        return {name: self._params[name].detach() for name, _ in self._base_table}
+
+    def lora_state_dict(self):
+        self.wait_tail_params()
+        return {name: self._params[name].detach() for name, _ in self._table[len(self._base_table):]}
+
+    def load_lora_state_dict(self, sd: Dict[str, torch.Tensor]):
+        names = [name for name, _ in self._table[len(self._base_table):]]
+        if set(sd) != set(names):
+            raise KeyError(f"adapter tensors do not match this UNet's LoraSpec: {sorted(set(sd) ^ set(names))[:4]} ...")
+        with torch.no_grad():
+            for name in names:
+                if tuple(sd[name].shape) != tuple(self._params[name].shape):
+                    raise ValueError(f"{name}: shape {tuple(sd[name].shape)} != {tuple(self._params[name].shape)}")
+                self._params[name].copy_(sd[name].to(device=self.device, dtype=BF16))
+        self._wt_dirty = True
+        return self
+
+    def init_lora(self, seed: int):
+        """B = 0; A ~ U(-1/sqrt(K), 1/sqrt(K)) drawn on the CPU from one generator seeded with `seed`, in table order."""
+        g = torch.Generator().manual_seed(int(seed))
+        sd = {}
+        for name, shape in self._table[len(self._base_table):]:
+            if name.endswith(".lora_A.weight"):
+                sd[name] = (torch.rand(shape, generator=g) * 2.0 - 1.0) / math.sqrt(shape[1])
+            else:
+                sd[name] = torch.zeros(shape)
+        return self.load_lora_state_dict(sd)
+
+    def _lora_group(self, mods):
+        """The adapters of the projections `mods` (one linear() call: a single projection or the parts of a fused one), or None.
+        Stacked views: A [n r][K] / At [K][n r] (the n adapted parts side by side), B [n N][r] / Bt [n r][N]."""
+        key = tuple(mods)
+        g = self._lora_groups.get(key, False)
+        if g is not False:
+            return g
+        have = [(p, m) for p, m in enumerate(mods) if m + ".lora_A.weight" in self._slots]
+        g = None
+        if have:
+            r, n = self.lora.rank, len(have)
+            oA, stA, _ = self._slots[have[0][1] + ".lora_A.weight"]
+            oB, stB, _ = self._slots[have[0][1] + ".lora_B.weight"]
+            K, N = stA[1], stB[0]
+            for i, (_, m) in enumerate(have):
+                if self._slots[m + ".lora_A.weight"][0] != oA + i * r * K or self._slots[m + ".lora_B.weight"][0] != oB + i * N * r:
+                    raise AozoraError(f"adapters of {mods} are not adjacent in the flat buffer")
+            names = [m + sfx for _, m in have for sfx in (".lora_A.weight", ".lora_B.weight")]
+            fl = lambda buf, o, rows, cols: buf[o:o + rows * cols].view(rows, cols)
+            g = SimpleNamespace(parts=[p for p, _ in have], n=n, full=n == len(mods), r=r, N=N, K=K, s=self.lora.scale, names=names,
+                                A=fl(self.pflat, oA, n * r, K), GA=fl(self.gflat, oA, n * r, K), At=fl(self.wtflat, oA, K, n * r),
+                                B=fl(self.pflat, oB, n * N, r), GB=fl(self.gflat, oB, n * N, r), Bt=fl(self.wtflat, oB, n * r, N))
+        self._lora_groups[key] = g
+        return g
+
+    def _lora_trainable(self, g) -> bool:
+        return g is not None and any(self._trainable(n) for n in g.names)
+
+    def _lora_parts(self, g):
+        """(index in the stack, column part of the fused output, number of parts) per launch: one launch for a whole group."""
+        return [(0, 0, g.n)] if g.full else [(i, p, 1) for i, p in enumerate(g.parts)]
+
+    # Which kernel carries an adapter product follows tools/lora_time.py (profiles/lora_time.json): an az_lora_* kernel is used where it
+    # beats az_gemm_bf16 beyond the repeat spread, or where the general product cannot express the contract -- a factor s != 1, a small
+    # dimension that is no multiple of 8 (rank 4 and its 8-byte slices), `du` of several parts with s.  Everywhere else the general
+    # product in its accumulate form computes the same contract:
+    #   down   az_lora_down_bf16, except many rows at a stacked rank >= 64 (M = 16384, r = 64: 13.3 against 9.2 us)
+    #   up     az_gemm_bf16, except few rows at rank <= 32 (the text context: 5.2 against 7.3 us) and a fused q|k|v group of rank <= 16
+    #          at up to 4096 rows in ONE launch (22.2 against 25.6 us for three general products)
+    #   tall   az_gemm_bf16 (the adapter kernel loses at every shape: 24.1 against 15.5 us)
+    # The thresholds are attributes so that a test can reach both sides at small shapes; they choose speed, not the contract (the fp32
+    # summation order differs between the two kernels).
+    _LORA_DOWN_GEMM_ROWS, _LORA_DOWN_GEMM_RANK = 8192, 64
+    _LORA_UP_FEW_ROWS, _LORA_UP_FEW_RANK = 512, 32
+    _LORA_UP_FUSED_ROWS, _LORA_UP_FUSED_RANK = 4096, 16
+
+    def _lora_down(self, x, w, out):
+        """out = x w^T (the stacked down matrices: x is read once)."""
+        R = w.shape[0]
+        if R % 8 == 0 and R >= self._LORA_DOWN_GEMM_RANK and x.shape[0] >= self._LORA_DOWN_GEMM_ROWS:
+            ops.gemm(x, w, out, trans_b=True)
+        else:
+            ops.lora_down(x, w, out)
+
+    def _lora_up(self, u, w, y, s, parts=1):
+        """y_p += s u_p w_p^T for the `parts` stacked parts."""
+        r, N, rows = w.shape[1], w.shape[0] // parts, u.shape[0]
+        own = (s != 1.0 or r % 8 != 0 or (rows <= self._LORA_UP_FEW_ROWS and r <= self._LORA_UP_FEW_RANK)
+               or (parts == 3 and rows <= self._LORA_UP_FUSED_ROWS and r <= self._LORA_UP_FUSED_RANK))
+        if own:
+            ops.lora_up(u, w, y, parts=parts, scale=s)
+            return
+        for p in range(parts):
+            ops.gemm(u[:, p * r:(p + 1) * r], w[p * N:(p + 1) * N], y[:, p * N:(p + 1) * N], trans_b=True, accumulate=True)
+
+    @staticmethod
+    def _lora_tall(small, big, out, s, parts, small_major):
+        """out_p += s small_p^T big_p; out_p [ns][nb] (small_major) or [nb][ns]."""
+        ns, nb = small.shape[1] // parts, big.shape[1] // parts
+        if s == 1.0 and ns % 8 == 0:
+            for p in range(parts):
+                sp, bp = small[:, p * ns:(p + 1) * ns], big[:, p * nb:(p + 1) * nb]
+                if small_major:
+                    ops.gemm(sp, bp, out[p * ns:(p + 1) * ns], trans_a=True, trans_b=False, accumulate=True, split_k=0)
+                else:
+                    ops.gemm(bp, sp, out[p * nb:(p + 1) * nb], trans_a=True, trans_b=False, accumulate=True, split_k=0)
+        else:
+            ops.lora_wgrad(small, big, out, parts=parts, scale=s, accumulate=True, small_major=small_major)
+
+    def _lora_fwd(self, g, x, u, y):
+        """u = x A_cat^T (x read once), then y_p += s u_p B_p^T on the column slices of the fused output."""
+        self._lora_down(x, g.A, u)
+        for i, p, n in self._lora_parts(g):
+            self._lora_up(u[:, i * g.r:(i + n) * g.r], g.B[i * g.N:(i + n) * g.N], y[:, p * g.N:(p + n) * g.N], g.s, n)
+
+    def _lora_du(self, g, dy, du):
+        """du_p = s dy_p B_p over the transposed copies of the up matrices."""
+        for i, p, n in self._lora_parts(g):
+            ops.lora_down(dy[:, p * g.N:(p + n) * g.N], g.Bt[i * g.r:(i + n) * g.r], du[:, i * g.r:(i + n) * g.r], parts=n, scale=g.s)
+
+    def _lora_wgrad(self, g, x, u, dy, du):
+        """dA_cat += du^T x; dB_p += s dy_p^T u_p."""
+        self._lora_tall(du, x, g.GA, 1.0, 1, True)
+        for i, p, n in self._lora_parts(g):
+            self._lora_tall(u[:, i * g.r:(i + n) * g.r], dy[:, p * g.N:(p + n) * g.N], g.GB[i * g.N:(i + n) * g.N], g.s, n, False)
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict=True):
         with torch.no_grad():
-            for name, _ in self._table:
+            for name, _ in self._base_table:
                 if name not in sd:
                     if strict:
                         raise KeyError(name)
@@ -821,7 +967,8 @@ class AozoraUNet:
 
     def linear(self, x: Act, wname: str, bname: Optional[str], residual: Optional[Act] = None,
                w_override: Optional[Tuple[torch.Tensor, torch.Tensor, bool]] = None, out: Optional[Act] = None,
-               pre: Optional[Act] = None, side_dgrad: bool = False, geglu_out: Optional[Act] = None) -> Act:
+               pre: Optional[Act] = None, side_dgrad: bool = False, geglu_out: Optional[Act] = None,
+               lora_mods: Optional[List[str]] = None) -> Act:
         """pre: the forward product was already computed by a grouped launch (_hoist_shared_input_linears); only the backward
         closure is registered here, at the layer's own place on the tape.
         side_dgrad: the output's gradient is PRODUCED on the parameter-gradient branch (time_emb_proj: dY = the per-sample
@@ -829,7 +976,8 @@ class AozoraUNet:
         end of the backward pass (emb): the data gradient then runs on the branch too, in order behind its producer, instead
         of making the chain wait for the branch to catch up once per ResnetBlock2D.
         geglu_out: this linear is a GEGLU's projection: the product is issued as az_gemm_geglu_fwd_bf16, whose epilogue also
-        writes value * gelu(gate) into geglu_out (geglu(..., pre=geglu_out) then only registers the backward closure)."""
+        writes value * gelu(gate) into geglu_out (geglu(..., pre=geglu_out) then only registers the backward closure).
+        lora_mods: the module names of the projections a w_override fuses (their adapters stay per projection)."""
         if w_override is not None:
             W, GW, w_train = w_override
         else:
@@ -848,11 +996,21 @@ class AozoraUNet:
                 ops.gemm(x.t, W, y.t, trans_b=True, bias=self._w[bname] if bname else None,
                          residual=residual.t if residual is not None else None,
                          split_k=0 if (rows <= 512 and residual is None) else 1)
+        lg = None
+        if self.lora is not None and geglu_out is None:
+            lg = self._lora_group(lora_mods if lora_mods is not None else ([wname[:-len(".weight")]] if wname else []))
+        if lg is not None:      # the adapter follows the base product (a hoisted one: here, at the layer's own place on the tape)
+            u = self._new(rows, lg.n * lg.r, need_grad=False)
+            self._lora_fwd(lg, x.t, u.t, y.t)
+            l_train = self._lora_trainable(lg)
 
         def bwd():
             dy = y.g
             if dy is None:
                 return
+            if lg is not None:
+                # taken whether or not the adapter is trainable (the pool's allocation order may not depend on the freeze mask)
+                du = self._new(rows, lg.n * lg.r, need_grad=False)
             on_side = side_dgrad and self.policy.temb_side and self.concurrent_wgrad and len(self._sides) == 1
             if on_side:
                 y.ready = None      # written on the branch, read on the branch
@@ -877,6 +1035,17 @@ class AozoraUNet:
                     self._finish_tn_jobs()
             elif w_train or b_train:
                 self._side_defer(wgrad)
+            if lg is not None:
+                if x.need_grad:
+                    self._lora_du(lg, dy, du.t)
+                if l_train:
+                    def lora_wgrad():
+                        # without an input gradient (the text context) nothing on the chain reads du, and dy may itself be produced on the
+                        # branch (the dK | dV kernel of a cross-attention): du then runs there too, in order behind its producer
+                        if not x.need_grad:
+                            self._lora_du(lg, dy, du.t)
+                        self._lora_wgrad(lg, x.t, u.t, dy, du.t)
+                    self._side_defer(lora_wgrad)
             if x.need_grad:
                 dx, add = self._gbuf(x)
                 oop = add is not None and add is not dx
@@ -884,6 +1053,8 @@ class AozoraUNet:
                 def dgrad():
                     ops.gemm(dy, WT, dx, trans_b=True, accumulate=add is dx, residual=add if oop else None,      # dX = dY . W  as  dY . (W^T)^T
                              split_k=0 if (rows <= 512 and not oop) else 1)
+                    if lg is not None:
+                        self._lora_up(du.t, lg.At, dx, 1.0)         # dx += du A_cat, directly behind the base product
                 if on_side:
                     self._side_defer(dgrad)
                     x.ready = self._flush_side()
@@ -1082,7 +1253,8 @@ class AozoraUNet:
         heads = C // self.cfg.head_dim
         scale = 1.0 / math.sqrt(self.cfg.head_dim)
         if ctx is None:
-            qkv = self.linear(x, None, None, w_override=self._fused_w([prefix + ".to_q.weight", prefix + ".to_k.weight", prefix + ".to_v.weight"]))
+            qkv = self.linear(x, None, None, w_override=self._fused_w([prefix + ".to_q.weight", prefix + ".to_k.weight", prefix + ".to_v.weight"]),
+                              lora_mods=[prefix + ".to_q", prefix + ".to_k", prefix + ".to_v"])
             q3 = qkv.t.view(B, T, 3 * C)[..., :C]
             k3 = qkv.t.view(B, T, 3 * C)[..., C:2 * C]
             v3 = qkv.t.view(B, T, 3 * C)[..., 2 * C:]
@@ -1090,8 +1262,9 @@ class AozoraUNet:
         else:
             q = self.linear(x, prefix + ".to_q.weight", None)
             kv_w = self._fused_w([prefix + ".to_k.weight", prefix + ".to_v.weight"])
-            kv_train = kv_w[2]
-            kv = self.linear(ctx, None, None, w_override=kv_w, pre=self._hoisted.pop(prefix + ".kv", None))
+            kv_mods = [prefix + ".to_k", prefix + ".to_v"]
+            kv_train = kv_w[2] or (self.lora is not None and self._lora_trainable(self._lora_group(kv_mods)))
+            kv = self.linear(ctx, None, None, w_override=kv_w, pre=self._hoisted.pop(prefix + ".kv", None), lora_mods=kv_mods)
             q3 = q.t.view(B, T, C)
             k3 = kv.t.view(B, ctx_len, 2 * C)[..., :C]
             v3 = kv.t.view(B, ctx_len, 2 * C)[..., C:]

@@ -133,3 +133,70 @@ def param_table(cfg: UNetConfig = SDXL_BASE):
     p += [("conv_norm_out.weight", (ch[0],)), ("conv_norm_out.bias", (ch[0],)),
           ("conv_out.weight", (cfg.out_channels, ch[0], 3, 3)), ("conv_out.bias", (cfg.out_channels,))]
     return p
+
+
+# --------------------------------------------------------------------------------------
+# LoRA adapters (INTEGRATION.md "LoRA"): which projections carry one, and their table entries
+# --------------------------------------------------------------------------------------
+LORA_RANKS = (4, 8, 16, 32, 64)
+LORA_PROJECTIONS = ("to_q", "to_k", "to_v", "to_out.0")       # of attn1 and attn2 of every BasicTransformerBlock
+
+
+@dataclass(frozen=True)
+class LoraSpec:
+    """rank-r adapters on the attention projections: y += (alpha / rank) (x A^T) B^T.  targets: comma-separated keywords read by
+    the freeze keywords' rule (fnmatch(name, kw if '*' in kw else '*kw*')) against the module names; '' or '*' = all eight."""
+    rank: int = 16
+    alpha: float = 16.0
+    targets: str = ""
+
+    def __post_init__(self):
+        if self.rank not in LORA_RANKS:
+            raise ValueError(f"LoRA rank {self.rank!r} is not one of {LORA_RANKS}")
+        if not (float(self.alpha) > 0.0):
+            raise ValueError(f"LoRA alpha must be > 0, got {self.alpha!r}")
+
+    @property
+    def scale(self) -> float:
+        return float(self.alpha) / self.rank
+
+
+def lora_modules(cfg: UNetConfig, spec: LoraSpec) -> List[str]:
+    """The adapted modules (names without '.weight') in parameter-table order.  A keyword that names a linear outside the
+    attention projections, or one that selects nothing, is refused."""
+    import fnmatch
+    kws = [k.strip() for k in (spec.targets or "").split(",") if k.strip()] or ["*"]
+    match = lambda name, kw: fnmatch.fnmatch(name, kw if "*" in kw else f"*{kw}*")
+    linears = [n[:-7] for n, shape in param_table(cfg) if n.endswith(".weight") and len(shape) == 2]
+    eligible = [m for m in linears if ".transformer_blocks." in m and (".attn1." in m or ".attn2." in m)]
+    out_of_scope = [m for m in linears if m not in eligible and (".attentions." in m or ".ff." in m)]
+    for kw in kws:
+        if any(match(m, kw) for m in eligible):
+            continue
+        other = [m for m in out_of_scope if match(m, kw)]
+        if other:
+            raise ValueError(f"LoRA target {kw!r} names {other[0]}: adapters on proj_in / proj_out and the feed-forward linears are "
+                             "out of scope (the GEGLU epilogue consumes the base product alone)")
+        raise ValueError(f"LoRA target {kw!r} selects no attention projection")
+    mods = [m for m in eligible if any(match(m, kw) for kw in kws)]
+    return mods
+
+
+def lora_table(cfg: UNetConfig, spec: LoraSpec):
+    """[(name, shape)] of the adapter parameters, appended behind conv_out.bias: per attention, the down matrices A [r][in] of its
+    fused group first (adjacent: one stacked operand), then the group's up matrices B [out][r], then to_out.0 (attn2: to_q first)."""
+    shapes = dict(param_table(cfg))
+    mods = set(lora_modules(cfg, spec))
+    attns = []
+    for m in lora_modules(cfg, spec):
+        a = m[:m.index(".to_")]
+        if a not in attns:
+            attns.append(a)
+    out = []
+    for a in attns:
+        groups = ([["to_q", "to_k", "to_v"], ["to_out.0"]] if a.endswith("attn1") else [["to_q"], ["to_k", "to_v"], ["to_out.0"]])
+        for g in groups:
+            names = [f"{a}.{p}" for p in g if f"{a}.{p}" in mods]
+            out += [(n + ".lora_A.weight", (spec.rank, shapes[n + ".weight"][1])) for n in names]
+            out += [(n + ".lora_B.weight", (shapes[n + ".weight"][0], spec.rank)) for n in names]
+    return out

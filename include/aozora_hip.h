@@ -525,6 +525,46 @@ int az_prodigy_finish(long npartials, const void* partials, void* dstate, void* 
 /* ref: not in the reference; stands where optimizer.step() does, train.py:2783 */
 int az_prodigy_apply(long n, void* p, void* w, const void* m, const void* v, const void* consts, void* stream);
 
+/* ---- LoRA adapter products (an option the reference does not have -- train.py is full fine-tuning only; INTEGRATION.md "LoRA
+ *      (`az_lora_*`)" states the arithmetic, tests/lora_ref.py restates it in float64) -------------------------------------------
+ * For a linear with base weight W[N][K], adapters A[r][K] ("down") and B[N][r] ("up") and s = alpha / r, all bf16, sums in fp32:
+ *     forward   u  = bf16(x A^T)                      y  = bf16(float(y_base) + s (u B^T))
+ *     backward  du = bf16(s (dy B))                   dx = bf16(float(dx_base) + du A)
+ *               dA = bf16(float(dA_prev) + du^T x)    dB = bf16(float(dB_prev) + s (dy^T u))
+ * Three shape classes, one entry point each; all are NT products (both operands contiguous along the summed index) except the
+ * gradient, which sums over rows.  The backward data products therefore take TRANSPOSED copies of the adapters (B^T [r][N] for du,
+ * A^T [K][r] for dx), which the caller refreshes after an optimizer step (az_transpose_bf16).  `parts` (1..3) projections that the
+ * executor fuses (to_q|to_k|to_v, to_k|to_v) go in one launch: part p takes its operands at p * the part strides (elements).  The
+ * small dimension is a multiple of 4 and is padded to the MFMA's 16 inside the kernels, never in memory.  Rows at or beyond M and
+ * columns outside the addressed slices are neither read into a result nor written.  Deterministic: no floating-point atomics, so a
+ * replayed launch reproduces the eager one bit for bit.  Argument errors -1110 .. -1119.
+ *
+ * az_lora_down_bf16 (skinny output): out[m][p r + n] = bf16(s sum_k X[m][p x_part_stride + k] W_p[n][k]), n < r, W_p = W + p
+ *   w_part_stride, rows of W at ldw.  u = x A_cat^T is parts = 1 with r = the stacked rank R of the group (the down matrices are
+ *   adjacent, x is read once); du is parts = the group's with X = dY, x_part_stride = N and W = the stacked B^T copies.  K % 8 == 0;
+ *   r % 4 == 0, parts r <= 192; X, W 16-byte aligned with ldx, ldw and the part strides multiples of 8; out 8-byte aligned, ldo % 4 == 0.
+ * az_lora_up_bf16 (skinny k, read-modify-write): Y[m][p y_part_stride + n] = bf16(float(Y[..]) + s sum_{k < r} U[m][p u_part_stride
+ *   + k] W_p[n][k]), n < N.  y += s u B^T is parts = the group's with W = the stacked B (w_part_stride = N r) and Y_p the column
+ *   slices of the fused output; dx += du A_cat is parts = 1, r = R, W = the A_cat^T copy [K][R].  N % 4 == 0, r % 4 == 0, r <= 192;
+ *   U, W, Y 8-byte aligned, every leading dimension and part stride a multiple of 4.
+ * az_lora_wgrad_bf16 (tall reduction): out[p out_part_stride + i_s out_stride_s + i_b out_stride_b] (+)= s sum_{m < M} S[m][p
+ *   s_part_stride + i_s] G[m][p g_part_stride + i_b], i_s < ns (the small operand: du or u), i_b < nb (x or dy).  dA_cat[R][K] is
+ *   out_stride_s = K, out_stride_b = 1; dB_p[N][r] is out_stride_s = 1, out_stride_b = r.  The rows are split into at most 64 ranges
+ *   (a function of the shapes and workspace_bytes only) whose fp32 partial sums go to `workspace` (parts * splits * ns * nb floats,
+ *   nothing in it survives the call); a second kernel adds them in ascending order, scales, adds the previous bf16 gradient when
+ *   `accumulate` and rounds once.  ns % 4 == 0, ns <= 192, nb % 8 == 0; S 8-byte aligned, ld_s and s_part_stride % 4 == 0; G 16-byte
+ *   aligned, ld_g and g_part_stride % 8 == 0. */
+/* ref: not in the reference (train.py:2760-2761 runs the un-adapted nn.Linear); follows the base product of an adapted projection */
+int az_lora_down_bf16(int M, int K, int r, int parts, float s, const void* X, long ldx, long x_part_stride, const void* W, long ldw,
+                      long w_part_stride, void* out, long ldo, void* stream);
+/* ref: not in the reference (same) */
+int az_lora_up_bf16(int M, int N, int r, int parts, float s, const void* U, long ldu, long u_part_stride, const void* W, long ldw,
+                    long w_part_stride, void* Y, long ldy, long y_part_stride, void* stream);
+/* ref: not in the reference; stands beside the weight gradients of train.py:2765 */
+int az_lora_wgrad_bf16(int M, int ns, int nb, int parts, float s, const void* S, long ld_s, long s_part_stride, const void* G, long ld_g,
+                       long g_part_stride, void* out, long out_stride_s, long out_stride_b, long out_part_stride, int accumulate,
+                       void* workspace, long workspace_bytes, void* stream);
+
 /* ---- native launch tape: the executor seam (SURVEY.md 8b "az_unet_step") ----------------------------------------------------
  * The step's launch sequence is static (same entry points, pointers, streams and events every step of a resolution bucket).  The
  * host executor records it once; az_tape_play re-issues it from C: entry-point calls (arguments as 64-bit words: int / long by
