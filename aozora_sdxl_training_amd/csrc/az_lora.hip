@@ -1,7 +1,7 @@
 // LoRA adapter products (include/aozora_hip.h az_lora_*): three shapes of product with one tiny dimension, each on
 // v_mfma_f32_16x16x32_bf16 with the small dimension padded to 16 (or 32 as the k-depth) by zero FRAGMENTS -- never in memory.
 //   down  : OUT[M][r]   = s X[M][K] . W[r][K]^T          one pass over X; a block's 4 waves split the k-range, fixed-order sum
-//   up    : Y[M][N]    += s U[M][r] . W[N][r]^T          read-modify-write of Y, k-depth r
+//   up    : Y[M][N]    += s U[M][r] . W[N][r]^T          read-modify-write of Y, k-depth r (+ the GEGLU of ff.net.0.proj in the epilogue)
 //   wgrad : OUT[ns][nb] (+)= s S[M][ns]^T . G[M][nb]     sum over M: fp32 partials per row range, then a fixed-order second stage
 // All three use the operand order of az_gemm.hip (D^T = small-frag x big-frag), so a lane owns 4 consecutive output columns.
 // Operand maps of the MFMA: lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15], j = 0..7; the result
@@ -82,6 +82,23 @@ __global__ __launch_bounds__(256) void lora_down_kernel(int M, int K, int r, flo
   }
 }
 
+// One 16 x 16 tile of an up product, shared by lora_up_kernel and lora_up_geglu_kernel so that both give the same bits: the sum over
+// the KS 32-deep k-steps in ascending order (W fragment x U fragment: a lane owns 4 consecutive columns of its row), then the
+// epilogue bf16(float(previous) + s sum).
+template <int KS>
+__device__ __forceinline__ f32x4 up_tile_sum(const bf16_t* wrow, const bf16x8 (&uf)[KS], int kq, int r, bool wok) {
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) acc = mfma16(load_small8(wrow, ks * 32 + kq, r, wok), uf[ks], acc);
+  return acc;
+}
+__device__ __forceinline__ bf16x4 up_tile_out(bf16x4 y, f32x4 acc, float s) {
+  f32x4 o;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) o[i] = bf2f((bf16_t)y[i]) + s * acc[i];
+  return pack4(o);
+}
+
 // ---- up: Y[m][p yps + n] = bf16(float(Y) + s sum_{k < r} U[m][p ups + k] W_p[n][k]) -------------------------------------------------
 // A wave owns 16 rows and 128 columns of part blockIdx.z; its U fragments (KS k-steps of 32) are loaded once.
 template <int KS>
@@ -108,14 +125,55 @@ __global__ __launch_bounds__(256) void lora_up_kernel(int M, int N, int r, float
     const bool yok = mok && n4 < N;               // N % 4 == 0: a 4-group is inside or outside as a whole
     bf16x4 y = {0, 0, 0, 0};
     if (yok) y = *(const bf16x4*)(yrow + n4);     // issued with the W loads: one latency per tile, not two
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 acc = up_tile_sum<KS>(wrow, uf, kq, r, wok);
+    if (yok) *(bf16x4*)(yrow + n4) = up_tile_out(y, acc, s);
+  }
+}
+
+// ---- up + GEGLU: proj[m][n] = bf16(float(proj) + s sum_{k < r} U[m][k] W[n][k]), n < 2 H; out[m][h] = bf16(value * gelu(gate)) ------------
+// lora_up_kernel on the [M][2 H] projection of ff.net.0.proj with az_geglu_fwd in its epilogue.  A wave owns 16 rows and 64 VALUE
+// columns together with the 64 GATE columns H + n of the same n: two MFMA chains per 16-column tile (same operand order, same k-step
+// order, same epilogue expression as lora_up_kernel: proj gets that kernel's bits), both halves are packed and stored, and out is
+// formed from the PACKED values in registers -- the bits az_geglu_fwd computes from the stored proj, without reading it back.
+template <int KS>
+__global__ __launch_bounds__(256) void lora_up_geglu_kernel(int M, int H, int r, float s, const bf16_t* __restrict__ U, long ldu,
+                                                            const bf16_t* __restrict__ W, long ldw, bf16_t* P, long ldp,
+                                                            bf16_t* __restrict__ out, long ldo) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long m0 = ((long)blockIdx.y * 4 + wave) * 16;
+  if (m0 >= M) return;
+  const int li = lane & 15, kq = (lane >> 4) * 8;
+  const long m = m0 + li;
+  const bool mok = m < M;
+  const bf16_t* urow = U + (mok ? m : 0) * ldu;
+  bf16x8 uf[KS];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) acc = mfma16(load_small8(wrow, ks * 32 + kq, r, wok), uf[ks], acc);
+  for (int ks = 0; ks < KS; ++ks) uf[ks] = load_small8(urow, ks * 32 + kq, r, mok);
+  bf16_t* prow = P + (mok ? m : 0) * ldp;
+  bf16_t* orow = out + (mok ? m : 0) * ldo;
+  const int nbeg = blockIdx.x * 64, nend = min(H, nbeg + 64);
+  for (int n0 = nbeg; n0 < nend; n0 += 16) {
+    const int nw = n0 + li;
+    const bool wok = nw < H;
+    const bf16_t* wval = W + (long)(wok ? nw : 0) * ldw;
+    const bf16_t* wgate = wval + (long)H * ldw;
+    const int n4 = n0 + (lane >> 4) * 4;
+    const bool yok = mok && n4 < H;               // H % 8 == 0: a 4-group is inside or outside as a whole, in both halves
+    bf16x4 yv = {0, 0, 0, 0}, yg = {0, 0, 0, 0};
+    if (yok) {                                    // issued with the W loads: one latency per tile, not two
+      yv = *(const bf16x4*)(prow + n4);
+      yg = *(const bf16x4*)(prow + H + n4);
+    }
+    const f32x4 av = up_tile_sum<KS>(wval, uf, kq, r, wok);
+    const f32x4 ag = up_tile_sum<KS>(wgate, uf, kq, r, wok);
     if (yok) {
+      const bf16x4 pv = up_tile_out(yv, av, s), pg = up_tile_out(yg, ag, s);
+      *(bf16x4*)(prow + n4) = pv;
+      *(bf16x4*)(prow + H + n4) = pg;
       f32x4 o;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) o[i] = bf2f((bf16_t)y[i]) + s * acc[i];
-      *(bf16x4*)(yrow + n4) = pack4(o);
+      for (int i = 0; i < 4; ++i) o[i] = bf2f((bf16_t)pv[i]) * gelu_erf(bf2f((bf16_t)pg[i]));
+      *(bf16x4*)(orow + n4) = pack4(o);
     }
   }
 }
@@ -247,6 +305,30 @@ int az_lora_up_bf16(int M, int N, int r, int parts, float s, const void* U, long
   if (r <= 32) az_launch(lora_up_kernel<1>, grid, block, 0, st, M, N, r, s, u, ldu, u_part_stride, w, ldw, w_part_stride, y, ldy, y_part_stride);
   else if (r <= 64) az_launch(lora_up_kernel<2>, grid, block, 0, st, M, N, r, s, u, ldu, u_part_stride, w, ldw, w_part_stride, y, ldy, y_part_stride);
   else az_launch(lora_up_kernel<6>, grid, block, 0, st, M, N, r, s, u, ldu, u_part_stride, w, ldw, w_part_stride, y, ldy, y_part_stride);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+
+int az_lora_up_geglu_bf16(int M, int H, int r, float s, const void* U, long ldu, const void* W, long ldw, void* proj, long ldp, void* out,
+                          long ldo, void* stream) {
+  if (M <= 0) return AZ_ERR_ARG(120);
+  if (H <= 0 || (H & 7)) return AZ_ERR_ARG(121);
+  if (r < 4 || r > 64 || (r & 3)) return AZ_ERR_ARG(122);
+  if (!U || !W || !proj || !out || !al(U, 8) || !al(W, 8) || !al(proj, 8) || !al(out, 8)) return AZ_ERR_ARG(123);
+  if ((ldu & 3) || (ldw & 3) || (ldp & 3) || (ldo & 3) || ldu < r || ldw < r || ldp < 2L * H || ldo < H) return AZ_ERR_ARG(124);
+  // proj is read and written in place: neither the down product nor the GEGLU output may share a byte with it
+  const uintptr_t p0 = (uintptr_t)proj, p1 = p0 + (uintptr_t)(((long)(M - 1) * ldp + 2L * H) * 2);
+  const uintptr_t u0 = (uintptr_t)U, u1 = u0 + (uintptr_t)(((long)(M - 1) * ldu + r) * 2);
+  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(((long)(M - 1) * ldo + H) * 2);
+  if ((u0 < p1 && p0 < u1) || (o0 < p1 && p0 < o1)) return AZ_ERR_ARG(125);
+  const long gy = ((long)M + 63) / 64;
+  if (gy > 65535) return AZ_ERR_ARG(126);
+  const dim3 grid((unsigned)((H + 63) / 64), (unsigned)gy), block(256);
+  const bf16_t *u = (const bf16_t*)U, *w = (const bf16_t*)W;
+  bf16_t *p = (bf16_t*)proj, *o = (bf16_t*)out;
+  hipStream_t st = (hipStream_t)stream;
+  if (r <= 32) az_launch(lora_up_geglu_kernel<1>, grid, block, 0, st, M, H, r, s, u, ldu, w, ldw, p, ldp, o, ldo);
+  else az_launch(lora_up_geglu_kernel<2>, grid, block, 0, st, M, H, r, s, u, ldu, w, ldw, p, ldp, o, ldo);
   AZ_CHECK_LAUNCH();
   return AZ_OK;
 }

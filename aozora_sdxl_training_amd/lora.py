@@ -1,6 +1,7 @@
 """LoRA training (INTEGRATION.md "LoRA"; not in the reference, whose train.py is full fine-tuning only): the options of
 `LORA_PARAMS`, the adapter file in the kohya-ss layout that ComfyUI and A1111 load, the merged model, and the loader.  Host-side
-logic only; the arithmetic is az_lora_* (csrc/az_lora.hip) inside AozoraUNet.linear."""
+logic only; the arithmetic is az_lora_* (csrc/az_lora.hip) inside AozoraUNet.linear.  "scope" chooses the linears that may carry an
+adapter: the attention projections (the default) or every Linear of every Transformer2DModel (unet_spec.LoraSpec)."""
 from __future__ import annotations
 
 import json
@@ -10,9 +11,9 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import checkpoint as ckpt
-from .unet_spec import LORA_RANKS, LoraSpec, lora_modules
+from .unet_spec import LORA_RANKS, LORA_SCOPES, LoraSpec, lora_modules
 
-_KEYS = ("rank", "alpha", "targets", "save_merged")
+_KEYS = ("rank", "alpha", "targets", "save_merged", "scope")
 DP_REFUSAL = ("LORA_PARAMS under data parallel (more than one rank): the flat gradient exchange would move the whole frozen base's "
               "gradient (5 GB at SDXL size) for a few MB of adapters; run LoRA on one GPU")
 EMA_REFUSAL = "LORA_PARAMS with \"ema_decay\": the EMA's file writer knows only the full model (EMA of adapters is a follow-up)"
@@ -49,13 +50,16 @@ def options(config, world: int = 1, ema_decay=None, cfg=None) -> Tuple[Optional[
     targets = hp.get("targets", "") or ""
     if isinstance(targets, (list, tuple)):
         targets = ", ".join(str(t) for t in targets)
+    scope = hp.get("scope", "attention")
+    if not isinstance(scope, str) or scope.strip().lower() not in LORA_SCOPES:
+        raise ValueError(f"LORA_PARAMS: scope {scope!r} is not one of {list(LORA_SCOPES)}")
     if world > 1:
         raise ValueError(DP_REFUSAL)
     if ema_decay is not None:
         raise ValueError(EMA_REFUSAL)
-    spec = LoraSpec(rank_i, alpha, str(targets))
+    spec = LoraSpec(rank_i, alpha, str(targets), scope.strip().lower())
     from .unet_spec import SDXL_BASE
-    lora_modules(cfg if cfg is not None else SDXL_BASE, spec)        # a target that selects nothing / something out of scope
+    lora_modules(cfg if cfg is not None else SDXL_BASE, spec)        # a target that selects nothing / something outside the scope
     return spec, _as_bool(hp.get("save_merged", False))
 
 

@@ -373,6 +373,23 @@ def lora_up(u, w, y, *, parts=1, scale=1.0):
     return y
 
 
+def lora_up_geglu(u, w, proj, out, *, scale=1.0):
+    """proj += scale * u @ w^T in place and out = proj[:, :H] * gelu(proj[:, H:]) on the rounded proj (az_lora_up_geglu_bf16): the up
+    product of ff.net.0.proj with az_geglu_fwd in its epilogue.  u [M][r], w [2 H][r] (value rows, then gate rows), proj [M][2 H], out [M][H]."""
+    M, r, ldu = _rows(u)
+    H2, wr, ldw = _rows(w)
+    Mp, H2p, ldp = _rows(proj)
+    Mo, H, ldo = _rows(out)
+    _req(wr == r and H2 == 2 * H and (Mp, Mo, H2p) == (M, M, H2),
+         f"lora_up_geglu shapes u {tuple(u.shape)} w {tuple(w.shape)} proj {tuple(proj.shape)} out {tuple(out.shape)}")
+    _req(H % 8 == 0 and r % 4 == 0 and 4 <= r <= 64, f"lora_up_geglu: H {H} % 8, rank {r} % 4 and <= 64")
+    _req(ldu % 4 == 0 and ldw % 4 == 0 and ldp % 4 == 0 and ldo % 4 == 0 and u.data_ptr() % 8 == 0 and w.data_ptr() % 8 == 0
+         and proj.data_ptr() % 8 == 0 and out.data_ptr() % 8 == 0, "lora_up_geglu: operand alignment")
+    with _prof("lora_up" + (f" {M}x{H2}x{r}+geglu" if PROFILE_SHAPES else ""), 2.0 * M * H2 * r, 2.0 * (2 * M * H2 + M * H + H2 * r + M * r)):
+        lib().call("az_lora_up_geglu_bf16", M, H, r, float(scale), _ptr(u), ldu, _ptr(w), ldw, _ptr(proj), ldp, _ptr(out), ldo, _stream())
+    return out
+
+
 def lora_wgrad(small, big, out, *, parts=1, scale=1.0, accumulate=True, small_major=True):
     """out (+)= scale * small_p^T @ big_p, summed over the rows (az_lora_wgrad_bf16).  small [M][parts * ns] (du or u), big [M][parts * nb]
     (x or dy).  small_major: out [parts * ns][nb] (dA_cat = du^T x); else out [parts * nb][ns] (the stacked dB_p = s dy_p^T u_p)."""

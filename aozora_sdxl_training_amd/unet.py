@@ -642,11 +642,18 @@ class AozoraUNet:
     #   up     az_gemm_bf16, except few rows at rank <= 32 (the text context: 5.2 against 7.3 us) and a fused q|k|v group of rank <= 16
     #          at up to 4096 rows in ONE launch (22.2 against 25.6 us for three general products)
     #   tall   az_gemm_bf16 (the adapter kernel loses at every shape: 24.1 against 15.5 us)
+    #   up + GEGLU (ff.net.0.proj; profiles/lora_ff_time.json)  az_lora_up_geglu_bf16 where the up product alone would be az_lora_up_bf16:
+    #          against that kernel + az_geglu_fwd it wins beyond the spread (M = 4096, H = 5120: 65.2 against 69.2 us at rank 16, 120.9
+    #          against 123.2 at rank 64; M = 16384, H = 2560, rank 16: 125.7 against 134.7), except many rows at rank 64, where two
+    #          MI355X disagreed (233.7 against 241.5 us on one, 251.3 against 244.0 on the other): the two-launch form there.  Where the
+    #          up product is the general product (s = 1, rank % 8 == 0, many rows) the fused kernel loses to it + az_geglu_fwd (65.3
+    #          against 56.2, 120.4 against 55.6, 125.5 against 101.4, 233.2 against 108.7 us): the two-launch form there too
     # The thresholds are attributes so that a test can reach both sides at small shapes; they choose speed, not the contract (the fp32
     # summation order differs between the two kernels).
     _LORA_DOWN_GEMM_ROWS, _LORA_DOWN_GEMM_RANK = 8192, 64
     _LORA_UP_FEW_ROWS, _LORA_UP_FEW_RANK = 512, 32
     _LORA_UP_FUSED_ROWS, _LORA_UP_FUSED_RANK = 4096, 16
+    _LORA_UP_GEGLU_ROWS, _LORA_UP_GEGLU_RANK = 8192, 64
 
     def _lora_down(self, x, w, out):
         """out = x w^T (the stacked down matrices: x is read once)."""
@@ -656,16 +663,29 @@ class AozoraUNet:
         else:
             ops.lora_down(x, w, out)
 
+    def _lora_up_own(self, rows, r, s, parts=1) -> bool:
+        """The up product goes to az_lora_up_bf16 (True) or to az_gemm_bf16 in its accumulate form (False)."""
+        return (s != 1.0 or r % 8 != 0 or (rows <= self._LORA_UP_FEW_ROWS and r <= self._LORA_UP_FEW_RANK)
+                or (parts == 3 and rows <= self._LORA_UP_FUSED_ROWS and r <= self._LORA_UP_FUSED_RANK))
+
     def _lora_up(self, u, w, y, s, parts=1):
         """y_p += s u_p w_p^T for the `parts` stacked parts."""
         r, N, rows = w.shape[1], w.shape[0] // parts, u.shape[0]
-        own = (s != 1.0 or r % 8 != 0 or (rows <= self._LORA_UP_FEW_ROWS and r <= self._LORA_UP_FEW_RANK)
-               or (parts == 3 and rows <= self._LORA_UP_FUSED_ROWS and r <= self._LORA_UP_FUSED_RANK))
-        if own:
+        if self._lora_up_own(rows, r, s, parts):
             ops.lora_up(u, w, y, parts=parts, scale=s)
             return
         for p in range(parts):
             ops.gemm(u[:, p * r:(p + 1) * r], w[p * N:(p + 1) * N], y[:, p * N:(p + 1) * N], trans_b=True, accumulate=True)
+
+    def _lora_up_geglu(self, u, w, proj, out, s):
+        """proj += s u w^T, then out = GEGLU(proj): az_lora_up_geglu_bf16 (one launch, proj read once) wherever _lora_up would take
+        az_lora_up_bf16, else the two-launch form (the general product, then az_geglu_fwd)."""
+        rows, r = u.shape[0], w.shape[1]
+        if self._lora_up_own(rows, r, s) and not (rows >= self._LORA_UP_GEGLU_ROWS and r >= self._LORA_UP_GEGLU_RANK):
+            ops.lora_up_geglu(u, w, proj, out, scale=s)
+        else:
+            self._lora_up(u, w, proj, s)
+            ops.geglu_fwd(proj, out)
 
     @staticmethod
     def _lora_tall(small, big, out, s, parts, small_major):
@@ -976,7 +996,8 @@ class AozoraUNet:
         end of the backward pass (emb): the data gradient then runs on the branch too, in order behind its producer, instead
         of making the chain wait for the branch to catch up once per ResnetBlock2D.
         geglu_out: this linear is a GEGLU's projection: the product is issued as az_gemm_geglu_fwd_bf16, whose epilogue also
-        writes value * gelu(gate) into geglu_out (geglu(..., pre=geglu_out) then only registers the backward closure).
+        writes value * gelu(gate) into geglu_out (geglu(..., pre=geglu_out) then only registers the backward closure).  With an
+        adapter the GEGLU must see the adapted projection: plain product, down product, then az_lora_up_geglu_bf16 writes geglu_out.
         lora_mods: the module names of the projections a w_override fuses (their adapters stay per projection)."""
         if w_override is not None:
             W, GW, w_train = w_override
@@ -985,23 +1006,28 @@ class AozoraUNet:
         N = W.shape[0]
         WT = self._wt(W) if x.need_grad else None
         rows = x.t.shape[0]
+        lg = None
+        if self.lora is not None:
+            lg = self._lora_group(lora_mods if lora_mods is not None else ([wname[:-len(".weight")]] if wname else []))
         if pre is not None:
             y = pre
         else:
             y = out if out is not None else self._new(rows, N)
-            if geglu_out is not None:
+            if geglu_out is not None and lg is None:
                 ops.gemm_geglu_fwd(x.t, W, self._w[bname] if bname else None, y.t, geglu_out.t)
             else:
                 # few-row products (the K/V projections of the 77-token context: 48 tiles) split along k to cover more CUs
+                # (an adapted GEGLU projection: the plain product -- the GEGLU follows the adapter, in _lora_up_geglu)
                 ops.gemm(x.t, W, y.t, trans_b=True, bias=self._w[bname] if bname else None,
                          residual=residual.t if residual is not None else None,
                          split_k=0 if (rows <= 512 and residual is None) else 1)
-        lg = None
-        if self.lora is not None and geglu_out is None:
-            lg = self._lora_group(lora_mods if lora_mods is not None else ([wname[:-len(".weight")]] if wname else []))
         if lg is not None:      # the adapter follows the base product (a hoisted one: here, at the layer's own place on the tape)
             u = self._new(rows, lg.n * lg.r, need_grad=False)
-            self._lora_fwd(lg, x.t, u.t, y.t)
+            if geglu_out is not None:
+                self._lora_down(x.t, lg.A, u.t)
+                self._lora_up_geglu(u.t, lg.B, y.t, geglu_out.t, lg.s)
+            else:
+                self._lora_fwd(lg, x.t, u.t, y.t)
             l_train = self._lora_trainable(lg)
 
         def bwd():

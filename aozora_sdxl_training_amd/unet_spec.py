@@ -140,21 +140,27 @@ def param_table(cfg: UNetConfig = SDXL_BASE):
 # --------------------------------------------------------------------------------------
 LORA_RANKS = (4, 8, 16, 32, 64)
 LORA_PROJECTIONS = ("to_q", "to_k", "to_v", "to_out.0")       # of attn1 and attn2 of every BasicTransformerBlock
+LORA_SCOPES = ("attention", "transformer")
 
 
 @dataclass(frozen=True)
 class LoraSpec:
-    """rank-r adapters on the attention projections: y += (alpha / rank) (x A^T) B^T.  targets: comma-separated keywords read by
-    the freeze keywords' rule (fnmatch(name, kw if '*' in kw else '*kw*')) against the module names; '' or '*' = all eight."""
+    """rank-r adapters: y += (alpha / rank) (x A^T) B^T.  scope: which linears may carry one -- "attention" (the default): the eight
+    attention projections of every BasicTransformerBlock; "transformer": every Linear of every Transformer2DModel (proj_in, the eight
+    projections, ff.net.0.proj, ff.net.2, proj_out: the default of the kohya-ss layout).  targets: comma-separated keywords read by
+    the freeze keywords' rule (fnmatch(name, kw if '*' in kw else '*kw*')) against the module names of the scope; '' or '*' = all."""
     rank: int = 16
     alpha: float = 16.0
     targets: str = ""
+    scope: str = "attention"
 
     def __post_init__(self):
         if self.rank not in LORA_RANKS:
             raise ValueError(f"LoRA rank {self.rank!r} is not one of {LORA_RANKS}")
         if not (float(self.alpha) > 0.0):
             raise ValueError(f"LoRA alpha must be > 0, got {self.alpha!r}")
+        if self.scope not in LORA_SCOPES:
+            raise ValueError(f"LoRA scope {self.scope!r} is not one of {LORA_SCOPES}")
 
     @property
     def scale(self) -> float:
@@ -162,12 +168,19 @@ class LoraSpec:
 
 
 def lora_modules(cfg: UNetConfig, spec: LoraSpec) -> List[str]:
-    """The adapted modules (names without '.weight') in parameter-table order.  A keyword that names a linear outside the
-    attention projections, or one that selects nothing, is refused."""
+    """The adapted modules (names without '.weight') in parameter-table order.  A keyword that names a linear outside the scope, or
+    one that selects nothing, is refused."""
     import fnmatch
     kws = [k.strip() for k in (spec.targets or "").split(",") if k.strip()] or ["*"]
     match = lambda name, kw: fnmatch.fnmatch(name, kw if "*" in kw else f"*{kw}*")
     linears = [n[:-7] for n, shape in param_table(cfg) if n.endswith(".weight") and len(shape) == 2]
+    if spec.scope == "transformer":
+        eligible = [m for m in linears if ".attentions." in m]
+        for kw in kws:
+            if not any(match(m, kw) for m in eligible):
+                raise ValueError(f"LoRA target {kw!r} selects no linear of a Transformer2DModel (scope \"transformer\": proj_in, the "
+                                 "attention projections, ff.net.0.proj, ff.net.2, proj_out)")
+        return [m for m in eligible if any(match(m, kw) for kw in kws)]
     eligible = [m for m in linears if ".transformer_blocks." in m and (".attn1." in m or ".attn2." in m)]
     out_of_scope = [m for m in linears if m not in eligible and (".attentions." in m or ".ff." in m)]
     for kw in kws:
@@ -183,20 +196,25 @@ def lora_modules(cfg: UNetConfig, spec: LoraSpec) -> List[str]:
 
 
 def lora_table(cfg: UNetConfig, spec: LoraSpec):
-    """[(name, shape)] of the adapter parameters, appended behind conv_out.bias: per attention, the down matrices A [r][in] of its
-    fused group first (adjacent: one stacked operand), then the group's up matrices B [out][r], then to_out.0 (attn2: to_q first)."""
+    """[(name, shape)] of the adapter parameters, appended behind conv_out.bias in the parameter-table order of their modules.  Per
+    attention, the down matrices A [r][in] of its fused group first (adjacent: one stacked operand), then the group's up matrices
+    B [out][r], then to_out.0 (attn2: to_q first).  Every other linear of scope "transformer" (proj_in, ff.net.0.proj, ff.net.2,
+    proj_out) is A, then B, at its module's place."""
     shapes = dict(param_table(cfg))
-    mods = set(lora_modules(cfg, spec))
-    attns = []
-    for m in lora_modules(cfg, spec):
-        a = m[:m.index(".to_")]
-        if a not in attns:
-            attns.append(a)
-    out = []
-    for a in attns:
-        groups = ([["to_q", "to_k", "to_v"], ["to_out.0"]] if a.endswith("attn1") else [["to_q"], ["to_k", "to_v"], ["to_out.0"]])
+    order = lora_modules(cfg, spec)
+    mods = set(order)
+    out, done = [], set()
+    for m in order:
+        if ".attn1." in m or ".attn2." in m:
+            a = m[:m.index(".to_")]
+            if a in done:
+                continue
+            done.add(a)
+            groups = ([["to_q", "to_k", "to_v"], ["to_out.0"]] if a.endswith("attn1") else [["to_q"], ["to_k", "to_v"], ["to_out.0"]])
+        else:
+            a, groups = None, [[m]]
         for g in groups:
-            names = [f"{a}.{p}" for p in g if f"{a}.{p}" in mods]
+            names = [f"{a}.{p}" for p in g if f"{a}.{p}" in mods] if a is not None else g
             out += [(n + ".lora_A.weight", (spec.rank, shapes[n + ".weight"][1])) for n in names]
             out += [(n + ".lora_B.weight", (shapes[n + ".weight"][0], spec.rank)) for n in names]
     return out

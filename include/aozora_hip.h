@@ -553,13 +553,26 @@ int az_prodigy_apply(long n, void* p, void* w, const void* m, const void* v, con
  *   (a function of the shapes and workspace_bytes only) whose fp32 partial sums go to `workspace` (parts * splits * ns * nb floats,
  *   nothing in it survives the call); a second kernel adds them in ascending order, scales, adds the previous bf16 gradient when
  *   `accumulate` and rounds once.  ns % 4 == 0, ns <= 192, nb % 8 == 0; S 8-byte aligned, ld_s and s_part_stride % 4 == 0; G 16-byte
- *   aligned, ld_g and g_part_stride % 8 == 0. */
+ *   aligned, ld_g and g_part_stride % 8 == 0.
+ * az_lora_up_geglu_bf16 (the up product of ff.net.0.proj with the GEGLU in its epilogue; argument errors -1120 .. -1126):
+ *     proj[m][n] = bf16(float(proj[m][n]) + s sum_{k < r} U[m][k] W[n][k])                 n < 2 H   (az_lora_up_bf16, parts = 1)
+ *     out[m][h]  = bf16(float(proj[m][h]) * gelu_erf(float(proj[m][H + h])))               h < H     (az_geglu_fwd)
+ *   with the second line taken on the ROUNDED, stored proj -- the rule of az_gemm_geglu_fwd_bf16's epilogue, so az_geglu_bwd, which
+ *   re-reads proj, sees what the forward used.  U[M][r] is the down product, W[2 H][r] the up matrix (value rows, then gate rows),
+ *   proj[M][2 H] the base product plus bias, updated in place; out[M][H] is written.  proj comes out with az_lora_up_bf16's bits and
+ *   out with az_geglu_fwd's, in one launch and without the second read of proj.  One error number per rule, in this order: M > 0
+ *   (-1120); H > 0, H % 8 == 0 (-1121); 4 <= r <= 64, r % 4 == 0 (-1122); no null pointer, all four 8-byte aligned (-1123); every row
+ *   stride a multiple of 4 and at least its width r, r, 2 H, H (-1124); neither U nor out overlaps proj (-1125); M <= 64 * 65535
+ *   (-1126). */
 /* ref: not in the reference (train.py:2760-2761 runs the un-adapted nn.Linear); follows the base product of an adapted projection */
 int az_lora_down_bf16(int M, int K, int r, int parts, float s, const void* X, long ldx, long x_part_stride, const void* W, long ldw,
                       long w_part_stride, void* out, long ldo, void* stream);
 /* ref: not in the reference (same) */
 int az_lora_up_bf16(int M, int N, int r, int parts, float s, const void* U, long ldu, long u_part_stride, const void* W, long ldw,
                     long w_part_stride, void* Y, long ldy, long y_part_stride, void* stream);
+/* ref: not in the reference (train.py:2760-2761 runs the un-adapted GEGLU.proj Linear, then hidden * gelu(gate)) */
+int az_lora_up_geglu_bf16(int M, int H, int r, float s, const void* U, long ldu, const void* W, long ldw, void* proj, long ldp, void* out,
+                          long ldo, void* stream);
 /* ref: not in the reference; stands beside the weight gradients of train.py:2765 */
 int az_lora_wgrad_bf16(int M, int ns, int nb, int parts, float s, const void* S, long ld_s, long s_part_stride, const void* G, long ld_g,
                        long g_part_stride, void* out, long out_stride_s, long out_stride_b, long out_part_stride, int accumulate,

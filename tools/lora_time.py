@@ -10,12 +10,18 @@
               wgrad  dA += du^T x          [r][K]  += [M][r]^T . [M][K]          vs  gemm tn, accumulate, split_k auto
             AozoraUNet._lora_up / _lora_tall route a product to the side that wins here (the general product where s = 1 and the rank is a
             multiple of 8 allow it).
-  step:     one micro-step at 1024^2, B = 4: rank 16, alpha 16 on all eight targets with the base frozen, against the full fine-tune
-            micro-step (everything trainable) of the SAME tree with LoRA off, alternated in one process; and the number of launches each
-            records on its tape.  (With LoRA off this tree issues the parent commit's launches: profiles/lora_bench_ab.json holds the
-            alternated bench.py runs of the two builds.)
+  geglu:    az_lora_up_geglu_bf16 (the up product of ff.net.0.proj with the GEGLU in its epilogue) against the two-launch form -- the up
+            product as AozoraUNet._lora_up issues it today (az_lora_up_bf16 or accumulate-az_gemm_bf16), then az_geglu_fwd -- at
+            M = 4096, H = 5120 and M = 16384, H = 2560, rank 16 and 64, s = 1 and s = 1/2.  Same procedure as `kernels`.
+            AozoraUNet._lora_up_geglu issues the side that wins here (profiles/lora_ff_time.json).
+  step:     one micro-step at 1024^2, B = 4: rank 16, alpha 16 with the base frozen -- scope "attention" (all eight projections) and
+            scope "transformer" (every Linear of every Transformer2DModel) -- against the full fine-tune micro-step (everything
+            trainable) of the SAME tree with LoRA off, alternated in one process; and the number of launches each records on its tape.
+            (With LoRA off this tree issues the parent commit's launches: profiles/lora_bench_ab.json and lora_ff_bench_ab.json hold
+            the alternated bench.py runs of the builds.)
 
-    python tools/lora_time.py [--reps 9] [--inner 200] [--no-step] [--out FILE]      -> one JSON line (also written to FILE)"""
+    python tools/lora_time.py [--reps 9] [--inner 200] [--no-kernels] [--no-geglu] [--no-step] [--out FILE]
+                                                                                     -> one JSON line (also written to FILE)"""
 import argparse
 import json
 import os
@@ -30,6 +36,7 @@ import torch  # noqa: E402
 DEV = "cuda:0"
 SHAPES = [("self M=16384 C=640", 16384, 640, 640), ("self M=4096 C=1280", 4096, 1280, 1280), ("context M=308 K=2048 N=1280", 308, 2048, 1280)]
 RANKS = (16, 64)
+GEGLU_SHAPES = [("ff M=4096 H=5120", 4096, 5120), ("ff M=16384 H=2560", 16384, 2560)]
 
 
 def taped(fn, inner):
@@ -100,6 +107,29 @@ def kernels(reps, inner):
     return out
 
 
+def geglu_kernels(reps, inner):
+    from aozora_sdxl_training_amd import ops
+    from aozora_sdxl_training_amd.unet import AozoraUNet
+    g = torch.Generator(device=DEV).manual_seed(1)
+    rnd = lambda *s: (torch.randn(*s, generator=g, device=DEV) * 0.05).bfloat16()
+    rule = object.__new__(AozoraUNet)          # _lora_up reads only the class's thresholds: no model is built
+    out = {}
+    for label, M, H in GEGLU_SHAPES:
+        for r in RANKS:
+            u, B, proj, o = rnd(M, r), rnd(2 * H, r), rnd(M, 2 * H), rnd(M, H)
+            proj2, o2 = proj.clone(), o.clone()
+            for s in (1.0, 0.5):
+                def two(s=s):
+                    rule._lora_up(u, B, proj2, s)
+                    ops.geglu_fwd(proj2, o2)
+                res = ab(lambda s=s: ops.lora_up_geglu(u, B, proj, o, scale=s), two, reps, inner)
+                res = dict(fused=res["lora"], two_launch=res["gemm"], fused_wins_beyond_spread=res["lora_wins_beyond_spread"],
+                           two_launch_wins_beyond_spread=bool(res["lora"]["median_us"] - res["gemm"]["median_us"] >
+                                                              max(res["lora"]["spread_us"], res["gemm"]["spread_us"])))
+                out[f"{label} r={r} s={s:g}"] = res
+    return out
+
+
 def step_ab(rounds, per_round):
     from bench import init_weights_on_device, synthetic_batch
     from aozora_sdxl_training_amd._lib import Call
@@ -108,7 +138,7 @@ def step_ab(rounds, per_round):
     from aozora_sdxl_training_amd.unet_spec import SDXL_BASE, LoraSpec
     batch = synthetic_batch(0, 0, 0, 4, DEV)
     sides = {}
-    for name, spec in (("full", None), ("lora", LoraSpec(16, 16.0))):
+    for name, spec in (("full", None), ("lora", LoraSpec(16, 16.0)), ("lora_transformer", LoraSpec(16, 16.0, "", "transformer"))):
         unet = AozoraUNet(SDXL_BASE, DEV, lora=spec)
         init_weights_on_device(unet)
         if spec is not None:
@@ -139,6 +169,7 @@ def step_ab(rounds, per_round):
     if launches["full"] and launches["lora"]:
         res["lora_launches_minus_full"] = launches["lora"] - launches["full"]
     res["lora_over_full"] = round(res["lora"]["median_ms"] / res["full"]["median_ms"], 4)
+    res["lora_transformer_over_full"] = round(res["lora_transformer"]["median_ms"] / res["full"]["median_ms"], 4)
     return res
 
 
@@ -149,11 +180,17 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--per-round", type=int, default=4)
     ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--no-geglu", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("lora_time needs a GPU")
-    rep = dict(tool="tools/lora_time.py", device=torch.cuda.get_device_name(0), kernels=kernels(a.reps, a.inner))
+    rep = dict(tool="tools/lora_time.py", device=torch.cuda.get_device_name(0))
+    if not a.no_kernels:
+        rep["kernels"] = kernels(a.reps, a.inner)
+    if not a.no_geglu:
+        rep["up_geglu"] = geglu_kernels(a.reps, a.inner)
     if not a.no_step:
         rep["micro_step_1024_B4_rank16"] = step_ab(a.rounds, a.per_round)
     line = json.dumps(rep, sort_keys=True)
