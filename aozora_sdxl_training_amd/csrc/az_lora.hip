@@ -6,6 +6,7 @@
 // All three use the operand order of az_gemm.hip (D^T = small-frag x big-frag), so a lane owns 4 consecutive output columns.
 // Operand maps of the MFMA: lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15], j = 0..7; the result
 // D[row = 4 (l >> 4) + i][col = l & 15], i = 0..3.  No floating-point atomics anywhere: every sum has a fixed order.
+// Behind them, the same three shapes for an adapter on a 3x3 convolution (az_lora_conv_*): the big operand gathered over the nine taps.
 #include "az_common.h"
 #include "aozora_hip.h"
 
@@ -263,7 +264,195 @@ __global__ __launch_bounds__(256) void lora_wgrad_finish_kernel(int ns, int nb, 
   *o = f2bf(v);
 }
 
+// ==== adapters on 3x3 convolutions (stride 1, pad 1; az_lora_conv_*) ================================================================
+// The same three shapes of product with the big operand GATHERED: row m = (b, h, w) of an NHWC activation [B H W][C] (any row stride)
+// meets, at tap t = 3 kh + kw, the row of pixel (h + kh - 1, w + kw - 1) of the SAME image.  A tap outside the image is a zero
+// fragment and never a load.  k = t Cin + c is the summed index of the down product and the column index of the weight gradient
+// (A is stored [r][3][3][Cin]: a row of A is one k-contiguous vector of 9 Cin elements; Cin % 8 == 0, so an 8-chunk never straddles
+// two taps); the data gradient sums over (t, j) through the copy At [Cin][3][3][r] with the taps mirrored.
+
+// row of the neighbour (dh, dw) of pixel row m = (b, h, w), or -1 outside image b
+__device__ __forceinline__ long nbr_row(long m, int h, int w, int H, int W, int dh, int dw) {
+  return ((unsigned)(h + dh) < (unsigned)H && (unsigned)(w + dw) < (unsigned)W) ? m + (long)dh * W + dw : -1;
+}
+
+// ---- conv down: U[m][n] = bf16(s sum_t sum_c X[nbr(m, t)][c] A[n][t][c]) ------------------------------------------------------------
+// lora_down_kernel over the k-range 9 Cin with the row pointer re-derived per 8-chunk (its tap): a block owns 16 pixels, its 4 waves
+// deal the k-range among themselves in groups of KU 32-deep steps, wave 0 adds the other three partial sums in wave order.
+template <int NT, int KU>
+__global__ __launch_bounds__(256) void lora_conv_down_kernel(int M, int H, int W, int Cin, int r, float s, const bf16_t* __restrict__ X, long ldx,
+                                                             const bf16_t* __restrict__ A, bf16_t* __restrict__ U, long ldu) {
+  __shared__ f32x4 red[3][NT][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long m0 = (long)blockIdx.x * 16;
+  const int li = lane & 15, kq = (lane >> 4) * 8;
+  const long m = m0 + li;
+  const bool mok = m < M;
+  const long pix = mok ? m : 0;
+  const int pw = (int)(pix % W), ph = (int)((pix / W) % H);
+  const int K = 9 * Cin;
+  const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  f32x4 acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k0 = wave * 32 * KU; k0 < K; k0 += 4 * 32 * KU) {
+    bf16x8 xf[KU], wf[KU][NT];
+#pragma unroll
+    for (int u = 0; u < KU; ++u) {
+      const int k = k0 + 32 * u + kq;
+      const bool kok = k < K;                     // K % 8 == 0: an 8-chunk is inside or outside as a whole
+      const int tap = kok ? k / Cin : 0, c = k - tap * Cin;
+      const long row = nbr_row(pix, ph, pw, H, W, tap / 3 - 1, tap % 3 - 1);
+      xf[u] = zero8;
+      if (mok && kok && row >= 0) xf[u] = *(const bf16x8*)(X + row * ldx + c);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int n = t * 16 + li;
+        wf[u][t] = zero8;
+        if (kok && n < r) wf[u][t] = *(const bf16x8*)(A + (long)n * K + k);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < KU; ++u) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) acc[t] = mfma16(wf[u][t], xf[u], acc[t]);
+    }
+  }
+  if (wave) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) red[wave - 1][t][lane] = acc[t];
+  }
+  __syncthreads();
+  if (wave || !mok) return;
+  bf16_t* urow = U + m * ldu;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int n4 = t * 16 + (lane >> 4) * 4;
+    const f32x4 v = ((acc[t] + red[0][t][lane]) + red[1][t][lane]) + red[2][t][lane];
+    if (n4 < r) *(bf16x4*)(urow + n4) = pack4(v * s);
+  }
+}
+
+// ---- conv dgrad: dX[m][c] = bf16(float(dX[m][c]) + s sum_t sum_{j < r} dU[nbr(m, mirrored t)][j] At[c][t][j]) ------------------------
+// lora_up_kernel with k = (tap, j): a wave owns 16 pixels and 128 channels; its dU fragments -- nine gathered rows, KS k-steps of 32
+// each, the rank padded by zero fragments -- are loaded once.  The sum runs over the taps in ascending order.
+template <int KS>
+__global__ __launch_bounds__(256) void lora_conv_dgrad_kernel(int M, int H, int W, int Cin, int r, float s, const bf16_t* __restrict__ dU, long ldu,
+                                                              const bf16_t* __restrict__ At, bf16_t* dX, long ldx) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long m0 = ((long)blockIdx.y * 4 + wave) * 16;
+  if (m0 >= M) return;
+  const int li = lane & 15, kq = (lane >> 4) * 8;
+  const long m = m0 + li;
+  const bool mok = m < M;
+  const long pix = mok ? m : 0;
+  const int pw = (int)(pix % W), ph = (int)((pix / W) % H);
+  bf16x8 uf[9][KS];
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap) {
+    const long row = nbr_row(pix, ph, pw, H, W, 1 - tap / 3, 1 - tap % 3);      // y[q] reads x[q + d]: x[p] is read by y[p - d]
+    const bool ok = mok && row >= 0;
+    const bf16_t* urow = dU + (ok ? row : 0) * ldu;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) uf[tap][ks] = load_small8(urow, ks * 32 + kq, r, ok);
+  }
+  bf16_t* xrow = dX + pix * ldx;
+  const int nbeg = blockIdx.x * 128, nend = min(Cin, nbeg + 128);
+  for (int n0 = nbeg; n0 < nend; n0 += 16) {
+    const int nw = n0 + li;
+    const bool wok = nw < Cin;
+    const bf16_t* wrow = At + (long)(wok ? nw : 0) * 9 * r;
+    const int n4 = n0 + (lane >> 4) * 4;
+    const bool yok = mok && n4 < Cin;             // Cin % 8 == 0: a 4-group is inside or outside as a whole
+    bf16x4 y = {0, 0, 0, 0};
+    if (yok) y = *(const bf16x4*)(xrow + n4);     // issued with the At loads: one latency per tile, not two
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) acc = mfma16(load_small8(wrow + tap * r, ks * 32 + kq, r, wok), uf[tap][ks], acc);
+    }
+    if (yok) *(bf16x4*)(xrow + n4) = up_tile_out(y, acc, s);
+  }
+}
+
+// ---- conv wgrad, stage 1: P[split][j][t Cin + c] = sum over the split's pixels of dU[m][j] X[nbr(m, t)][c] (fp32) ---------------------
+// lora_wgrad_partial_kernel whose big operand has 9 Cin gathered columns: a block owns 64 of them (8-chunks of one tap each), all
+// r columns of dU and one row range.  Stage 2 is lora_wgrad_finish_kernel (out strides 9 Cin, 1).
+template <int NT>
+__global__ __launch_bounds__(256) void lora_conv_wgrad_partial_kernel(int M, int H, int W, int Cin, int ns, int rps, const bf16_t* __restrict__ S, long ld_s,
+                                                                      const bf16_t* __restrict__ X, long ldx, float* __restrict__ P) {
+  __shared__ __attribute__((aligned(16))) bf16_t St[NT * 16 * LKP];
+  __shared__ __attribute__((aligned(16))) bf16_t Gt[64 * LKP];
+  constexpr int SQ = NT * 4;
+  constexpr int SI = (32 * SQ + 255) / 256;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int split = blockIdx.y, nb = 9 * Cin;
+  const int b0 = blockIdx.x * 64;
+  const long mbeg = (long)split * rps, mend = min((long)M, mbeg + rps);
+  const int li = lane & 15, kq = (lane >> 4) * 8;
+  const int grow = tid >> 3, gcol = b0 + (tid & 7) * 8;
+  const bool gok = gcol < nb;                      // nb % 8 == 0
+  const int gtap = gok ? gcol / Cin : 0, gc = gcol - gtap * Cin, gdh = gtap / 3 - 1, gdw = gtap % 3 - 1;
+  f32x4 acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  bf16x8 gv;
+  bf16x4 sv[SI];
+  auto load_slice = [&](long mk) {
+    gv = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    const long pix = mk + grow;
+    if (pix < mend && gok) {
+      const long row = nbr_row(pix, (int)((pix / W) % H), (int)(pix % W), H, W, gdh, gdw);
+      if (row >= 0) gv = *(const bf16x8*)(X + row * ldx + gc);
+    }
+#pragma unroll
+    for (int i = 0; i < SI; ++i) {
+      const int it = tid + i * 256, row = it / SQ, c4 = (it % SQ) * 4;
+      sv[i] = bf16x4{0, 0, 0, 0};
+      if (it < 32 * SQ && mk + row < mend && c4 < ns) sv[i] = *(const bf16x4*)(S + (mk + row) * ld_s + c4);  // ns % 4 == 0
+    }
+  };
+  load_slice(mbeg);
+  for (long mk = mbeg; mk < mend; mk += 32) {
+    __syncthreads();                               // the previous slice's fragments have been read
+#pragma unroll
+    for (int j = 0; j < 8; ++j) Gt[((tid & 7) * 8 + j) * LKP + grow] = (bf16_t)gv[j];
+#pragma unroll
+    for (int i = 0; i < SI; ++i) {
+      const int it = tid + i * 256, row = it / SQ, c4 = (it % SQ) * 4;
+      if (it < 32 * SQ) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) St[(c4 + j) * LKP + row] = (bf16_t)sv[i][j];
+      }
+    }
+    __syncthreads();
+    if (mk + 32 < mend) load_slice(mk + 32);
+    const bf16x8 gf = *(const bf16x8*)(Gt + (wave * 16 + li) * LKP + kq);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = mfma16(*(const bf16x8*)(St + (t * 16 + li) * LKP + kq), gf, acc[t]);
+  }
+  const int ib = b0 + wave * 16 + li;
+  if (ib >= nb) return;
+  float* Pp = P + (long)split * ns * nb;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int is = t * 16 + (lane >> 4) * 4 + i;
+      if (is < ns) Pp[(long)is * nb + ib] = acc[t][i];
+    }
+  }
+}
+
 inline bool al(const void* p, int a) { return ((uintptr_t)p & (uintptr_t)(a - 1)) == 0; }
+
+// the checks the three az_lora_conv_* entry points share: geometry, channel count, rank; -> B H W or 0
+inline long conv_rows(int B, int H, int W, int Cin, int r) {
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin & 7) || r < 4 || r > 64 || (r & 3)) return 0;
+  const long M = (long)B * H * W;
+  return (M > 0x7FFFFFF0L || 9L * Cin > 0x7FFFFFF0L) ? 0 : M;
+}
 
 }  // namespace
 
@@ -366,6 +555,78 @@ int az_lora_wgrad_bf16(int M, int ns, int nb, int parts, float s, const void* S,
   const long total = (long)parts * ns * nb;
   az_launch(lora_wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ns, nb, parts, nsplit, s, (const float*)P, (bf16_t*)out,
             out_stride_s, out_stride_b, out_part_stride, accumulate);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+
+int az_lora_conv_down_bf16(int B, int H, int W, int Cin, int r, float s, const void* X, long ldx, const void* A, void* out, long ldo,
+                           void* stream) {
+  const long M = conv_rows(B, H, W, Cin, r);
+  if (!M) return AZ_ERR_ARG(130);
+  if (!X || !A || !out || !al(X, 16) || !al(A, 16) || !al(out, 8)) return AZ_ERR_ARG(131);
+  if ((ldx & 7) || (ldo & 3) || ldx < Cin || ldo < r) return AZ_ERR_ARG(132);
+  const dim3 grid((unsigned)((M + 15) / 16)), block(256);
+  const bf16_t *x = (const bf16_t*)X, *a = (const bf16_t*)A;
+  bf16_t* u = (bf16_t*)out;
+  hipStream_t st = (hipStream_t)stream;
+  if (r <= 16) az_launch(lora_conv_down_kernel<1, 4>, grid, block, 0, st, (int)M, H, W, Cin, r, s, x, ldx, a, u, ldo);
+  else if (r <= 32) az_launch(lora_conv_down_kernel<2, 4>, grid, block, 0, st, (int)M, H, W, Cin, r, s, x, ldx, a, u, ldo);
+  else az_launch(lora_conv_down_kernel<4, 2>, grid, block, 0, st, (int)M, H, W, Cin, r, s, x, ldx, a, u, ldo);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+
+int az_lora_conv_dgrad_bf16(int B, int H, int W, int Cin, int r, float s, const void* dU, long ldu, const void* At, void* dX, long ldx,
+                            void* stream) {
+  const long M = conv_rows(B, H, W, Cin, r);
+  if (!M) return AZ_ERR_ARG(133);
+  if (!dU || !At || !dX || !al(dU, 8) || !al(At, 8) || !al(dX, 8)) return AZ_ERR_ARG(134);
+  if ((ldu & 3) || (ldx & 3) || ldu < r || ldx < Cin) return AZ_ERR_ARG(135);
+  // dX is read and written in place while neighbouring rows of dU are gathered: the two may not share a byte
+  const uintptr_t x0 = (uintptr_t)dX, x1 = x0 + (uintptr_t)(((M - 1) * ldx + Cin) * 2);
+  const uintptr_t u0 = (uintptr_t)dU, u1 = u0 + (uintptr_t)(((M - 1) * ldu + r) * 2);
+  if (u0 < x1 && x0 < u1) return AZ_ERR_ARG(135);
+  const long gy = (M + 63) / 64;
+  if (gy > 65535) return AZ_ERR_ARG(133);
+  const dim3 grid((unsigned)((Cin + 127) / 128), (unsigned)gy), block(256);
+  const bf16_t *du = (const bf16_t*)dU, *at = (const bf16_t*)At;
+  bf16_t* dx = (bf16_t*)dX;
+  hipStream_t st = (hipStream_t)stream;
+  if (r <= 32) az_launch(lora_conv_dgrad_kernel<1>, grid, block, 0, st, (int)M, H, W, Cin, r, s, du, ldu, at, dx, ldx);
+  else az_launch(lora_conv_dgrad_kernel<2>, grid, block, 0, st, (int)M, H, W, Cin, r, s, du, ldu, at, dx, ldx);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+
+int az_lora_conv_wgrad_bf16(int B, int H, int W, int Cin, int r, float s, const void* dU, long ldu, const void* X, long ldx, void* dA,
+                            int accumulate, void* workspace, long workspace_bytes, void* stream) {
+  const long M = conv_rows(B, H, W, Cin, r);
+  if (!M) return AZ_ERR_ARG(136);
+  if (!dU || !X || !dA || !workspace || !al(dU, 8) || !al(X, 16) || !al(dA, 2) || !al(workspace, 4)) return AZ_ERR_ARG(137);
+  if ((ldu & 3) || (ldx & 7) || ldu < r || ldx < Cin) return AZ_ERR_ARG(138);
+  // rows per split: the rule of az_lora_wgrad_bf16 with nb = 9 Cin gathered columns
+  const long nb = 9L * Cin, per = (long)r * nb * 4;
+  long cap = workspace_bytes / per;
+  if (cap < 1) return AZ_ERR_ARG(139);
+  const long base = (nb + 63) / 64;
+  long want = (512 + base - 1) / base;
+  if (want > 64) want = 64;
+  if (want > cap) want = cap;
+  const long slices = (M + 31) / 32;
+  if (want > slices) want = slices;
+  const long rps = ((slices + want - 1) / want) * 32;
+  const int nsplit = (int)((M + rps - 1) / rps);
+  const dim3 grid((unsigned)base, (unsigned)nsplit), block(256);
+  const bf16_t *sp = (const bf16_t*)dU, *xp = (const bf16_t*)X;
+  float* P = (float*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  if (r <= 16) az_launch(lora_conv_wgrad_partial_kernel<1>, grid, block, 0, st, (int)M, H, W, Cin, r, (int)rps, sp, ldu, xp, ldx, P);
+  else if (r <= 32) az_launch(lora_conv_wgrad_partial_kernel<2>, grid, block, 0, st, (int)M, H, W, Cin, r, (int)rps, sp, ldu, xp, ldx, P);
+  else az_launch(lora_conv_wgrad_partial_kernel<4>, grid, block, 0, st, (int)M, H, W, Cin, r, (int)rps, sp, ldu, xp, ldx, P);
+  AZ_CHECK_LAUNCH();
+  const long total = (long)r * nb;
+  az_launch(lora_wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, r, (int)nb, 1, nsplit, s, (const float*)P, (bf16_t*)dA,
+            nb, 1L, 0L, accumulate);
   AZ_CHECK_LAUNCH();
   return AZ_OK;
 }

@@ -1,7 +1,8 @@
 """LoRA training (INTEGRATION.md "LoRA"; not in the reference, whose train.py is full fine-tuning only): the options of
 `LORA_PARAMS`, the adapter file in the kohya-ss layout that ComfyUI and A1111 load, the merged model, and the loader.  Host-side
 logic only; the arithmetic is az_lora_* (csrc/az_lora.hip) inside AozoraUNet.linear.  "scope" chooses the linears that may carry an
-adapter: the attention projections (the default) or every Linear of every Transformer2DModel (unet_spec.LoraSpec)."""
+adapter: the attention projections (the default), every Linear of every Transformer2DModel, or those and the convolutions of every
+ResnetBlock2D ("unet": conv1 / conv2 at `conv_rank` / `conv_alpha`, kohya-ss conv_dim / conv_alpha; unet_spec.LoraSpec)."""
 from __future__ import annotations
 
 import json
@@ -11,9 +12,10 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import checkpoint as ckpt
-from .unet_spec import LORA_RANKS, LORA_SCOPES, LoraSpec, lora_modules
+from .unet_spec import LORA_RANKS, LORA_SCOPES, LoraSpec, lora_is_conv3, lora_modules
 
 _KEYS = ("rank", "alpha", "targets", "save_merged", "scope")
+_CONV_KEYS = ("conv_rank", "conv_alpha")        # of "scope": "unet"
 DP_REFUSAL = ("LORA_PARAMS under data parallel (more than one rank): the flat gradient exchange would move the whole frozen base's "
               "gradient (5 GB at SDXL size) for a few MB of adapters; run LoRA on one GPU")
 EMA_REFUSAL = "LORA_PARAMS with \"ema_decay\": the EMA's file writer knows only the full model (EMA of adapters is a follow-up)"
@@ -31,9 +33,9 @@ def options(config, world: int = 1, ema_decay=None, cfg=None) -> Tuple[Optional[
         return None, False
     if not isinstance(hp, dict):
         raise ValueError(f"LORA_PARAMS must be a dictionary, got {type(hp).__name__}")
-    unknown = sorted(k for k in hp if k not in _KEYS)
+    unknown = sorted(k for k in hp if k not in _KEYS + _CONV_KEYS)
     if unknown:
-        raise ValueError(f"LORA_PARAMS holds unknown key(s) {unknown}: this build reads {list(_KEYS)}")
+        raise ValueError(f"LORA_PARAMS holds unknown key(s) {unknown}: this build reads {list(_KEYS + _CONV_KEYS)}")
     rank = hp.get("rank", 16)
     if isinstance(rank, (list, tuple, dict)):
         raise ValueError(f"LORA_PARAMS: one rank for all adapters, got {rank!r} (more than one rank is a follow-up)")
@@ -53,11 +55,35 @@ def options(config, world: int = 1, ema_decay=None, cfg=None) -> Tuple[Optional[
     scope = hp.get("scope", "attention")
     if not isinstance(scope, str) or scope.strip().lower() not in LORA_SCOPES:
         raise ValueError(f"LORA_PARAMS: scope {scope!r} is not one of {list(LORA_SCOPES)}")
+    scope = scope.strip().lower()
+    conv_rank, conv_alpha = hp.get("conv_rank"), hp.get("conv_alpha")
+    if (conv_rank is not None or conv_alpha is not None) and scope != "unet":
+        raise ValueError(f"LORA_PARAMS: conv_rank / conv_alpha belong to \"scope\": \"unet\" (scope {scope!r} adapts no convolution)")
+    if conv_rank is not None:
+        try:
+            if isinstance(conv_rank, (list, tuple, dict, bool)) or int(conv_rank) != float(conv_rank):
+                raise ValueError
+            conv_rank = int(conv_rank)
+        except (TypeError, ValueError):
+            raise ValueError(f"LORA_PARAMS: conv_rank cannot be read as one whole number: {conv_rank!r}") from None
+        if conv_rank not in LORA_RANKS:
+            raise ValueError(f"LORA_PARAMS: conv_rank {conv_rank} is not one of {list(LORA_RANKS)}")
+    if conv_alpha is not None:
+        try:
+            if isinstance(conv_alpha, bool):
+                raise ValueError
+            conv_alpha = float(conv_alpha)
+        except (TypeError, ValueError):
+            raise ValueError(f"LORA_PARAMS: conv_alpha cannot be read as a number: {conv_alpha!r}") from None
+        if not conv_alpha > 0.0:
+            raise ValueError(f"LORA_PARAMS: conv_alpha must be > 0, got {conv_alpha}")
     if world > 1:
         raise ValueError(DP_REFUSAL)
     if ema_decay is not None:
         raise ValueError(EMA_REFUSAL)
-    spec = LoraSpec(rank_i, alpha, str(targets), scope.strip().lower())
+    if scope == "unet" and conv_rank is None:
+        conv_rank = rank_i              # "conv_rank" left out = "rank" (a LoraSpec of scope "unet" names it)
+    spec = LoraSpec(rank_i, alpha, str(targets), scope, conv_rank, conv_alpha)
     from .unet_spec import SDXL_BASE
     lora_modules(cfg if cfg is not None else SDXL_BASE, spec)        # a target that selects nothing / something outside the scope
     return spec, _as_bool(hp.get("save_merged", False))
@@ -69,23 +95,36 @@ def file_key(module: str) -> str:
     return "lora_unet_" + ckpt._sd_name(module + ".weight")[:-len(".weight")].replace(".", "_")
 
 
+def _is_conv(module: str) -> bool:
+    """A convolution of a ResnetBlock2D: its file tensors are 4-D (the 1x1 conv_shortcut too, with trailing 1 x 1)."""
+    return lora_is_conv3(module) or (".resnets." in module and module.endswith(".conv_shortcut"))
+
+
 def file_tensors(lora_state: Dict[str, torch.Tensor], spec: LoraSpec) -> Dict[str, torch.Tensor]:
+    """A linear: lora_down [r][in], lora_up [out][r].  A convolution (kohya-ss): lora_down [r][Cin][kh][kw] -- the logical shape of A,
+    a permutation of its device layout [r][kh][kw][Cin] -- and lora_up [Cout][r][1][1].  .alpha is the module's own alpha."""
     out = {}
     for name, t in lora_state.items():
         module, _, leaf = name.rpartition(".lora_")
         key = file_key(module)
-        out[key + (".lora_down.weight" if leaf == "A.weight" else ".lora_up.weight")] = t.detach().to("cpu", torch.bfloat16).contiguous()
-        out[key + ".alpha"] = torch.tensor(float(spec.alpha), dtype=torch.bfloat16)
+        t = t.detach().to("cpu", torch.bfloat16)
+        if _is_conv(module) and t.dim() == 2:
+            t = t[:, :, None, None]
+        out[key + (".lora_down.weight" if leaf == "A.weight" else ".lora_up.weight")] = t.contiguous()
+        out[key + ".alpha"] = torch.tensor(spec.alpha_of(module), dtype=torch.bfloat16)
     return out
 
 
 def file_metadata(spec: LoraSpec) -> Dict[str, str]:
-    return {"ss_network_module": "networks.lora", "ss_network_dim": str(spec.rank), "ss_network_alpha": f"{float(spec.alpha):g}",
+    meta = {"ss_network_module": "networks.lora", "ss_network_dim": str(spec.rank), "ss_network_alpha": f"{float(spec.alpha):g}",
             "ss_base_model_version": "sdxl_base_v1-0"}
+    if spec.scope == "unet":
+        meta["ss_network_args"] = json.dumps({"conv_dim": str(spec.conv3_rank), "conv_alpha": f"{spec.conv3_alpha:g}"})
+    return meta
 
 
 def save_lora_file(path, unet, spec: Optional[LoraSpec] = None):
-    """Write ONLY the adapters: <key>.lora_down.weight [r][in], .lora_up.weight [out][r], .alpha (0-dim), bf16."""
+    """Write ONLY the adapters: <key>.lora_down.weight [r][in], .lora_up.weight [out][r] (convolutions: file_tensors), .alpha (0-dim), bf16."""
     from safetensors.torch import save_file
     spec = spec if spec is not None else unet.lora
     path = Path(path)
@@ -105,31 +144,44 @@ def read_lora_file(path, unet) -> Dict[str, torch.Tensor]:
         meta = f.metadata() or {}
         if meta.get("ss_network_dim") not in (None, str(spec.rank)):
             raise ValueError(f"{Path(path).name} holds rank {meta.get('ss_network_dim')} adapters; LORA_PARAMS asks for rank {spec.rank}")
+        state = unet.lora_state_dict()
         want = set()
-        for name in unet.lora_state_dict():
+        for name in state:
+            module = name.rpartition(".lora_")[0]
+            want.update((file_key(module) + (".lora_down.weight" if name.endswith("A.weight") else ".lora_up.weight"), file_key(module) + ".alpha"))
+        # keys the scope does not carry (a file with adapters on emb_layers, op, conv ... of a wider network): named, not dropped
+        extra = sorted(keys - want)
+        if extra:
+            raise KeyError(f"{Path(path).name} holds adapters this LoraSpec does not, the first of them {extra[0]} ({len(extra)} keys in all)")
+        for name, mine in state.items():
             module, _, leaf = name.rpartition(".lora_")
             k = file_key(module) + (".lora_down.weight" if leaf == "A.weight" else ".lora_up.weight")
-            want.update((k, file_key(module) + ".alpha"))
             if k not in keys:
                 raise KeyError(f"{k} is missing from {Path(path).name}")
-            out[name] = f.get_tensor(k)
+            t = f.get_tensor(k)
+            if t.numel() != mine.numel() or tuple(t.shape[:2]) != tuple(mine.shape[:2]):
+                raise ValueError(f"{Path(path).name}: {k} has shape {tuple(t.shape)}; this LoraSpec gives {module} {tuple(mine.shape)}")
+            out[name] = t.reshape(tuple(mine.shape))       # a convolution's up matrix and conv_shortcut carry a trailing 1 x 1 in the file
             a = float(f.get_tensor(file_key(module) + ".alpha"))
-            if a != float(torch.tensor(float(spec.alpha), dtype=torch.bfloat16)):
-                raise ValueError(f"{Path(path).name}: alpha {a} of {module} differs from LORA_PARAMS' {spec.alpha}")
-        if keys != want:
-            raise KeyError(f"{Path(path).name} holds adapters this LoraSpec does not: {sorted(keys - want)[:3]}")
+            if a != float(torch.tensor(spec.alpha_of(module), dtype=torch.bfloat16)):
+                raise ValueError(f"{Path(path).name}: alpha {a} of {module} differs from LORA_PARAMS' {spec.alpha_of(module)}")
     return out
 
 
 def merged_state(unet) -> Dict[str, torch.Tensor]:
-    """The base state dict with W + s B A in place of every adapted weight: formed in fp32 on the CPU, rounded once (by save_model)."""
-    sd = {k: v.detach().cpu() for k, v in unet.state_dict().items()}
-    ls = {k: v.detach().float().cpu() for k, v in unet.lora_state_dict().items()}
-    s = unet.lora.scale
+    """The base state dict with W + s B A in place of every adapted weight -- a 3x3 convolution: W[o][c][kh][kw] + s sum_j B[o][j]
+    A[j][c][kh][kw] -- formed in fp32 on the CPU, rounded once (by save_model).  s is the module's own alpha / rank."""
+    return merge_into({k: v.detach().cpu() for k, v in unet.state_dict().items()},
+                      {k: v.detach().float().cpu() for k, v in unet.lora_state_dict().items()}, unet.lora)
+
+
+def merge_into(sd: Dict[str, torch.Tensor], ls: Dict[str, torch.Tensor], spec: LoraSpec) -> Dict[str, torch.Tensor]:
     for name, A in ls.items():
         if name.endswith(".lora_A.weight"):
             module = name[:-len(".lora_A.weight")]
-            sd[module + ".weight"] = sd[module + ".weight"].float() + s * (ls[module + ".lora_B.weight"] @ A)
+            W, B = sd[module + ".weight"].float(), ls[module + ".lora_B.weight"].float()
+            delta = (B @ A.float().reshape(A.shape[0], -1)).reshape(W.shape)      # [o][j] x [j][c kh kw]: the logical order of both
+            sd[module + ".weight"] = W + spec.scale_of(module) * delta
     return sd
 
 

@@ -410,6 +410,69 @@ def lora_wgrad(small, big, out, *, parts=1, scale=1.0, accumulate=True, small_ma
     return out
 
 
+def _lora_conv_geom(geom, x, what):
+    """(B, H, W) and an activation [B H W][C] (2-D rows, any row stride) -> (B, H, W, C, ld)."""
+    _req(len(geom) == 3 and all(int(v) > 0 for v in geom), f"{what}: geometry (B, H, W) {geom}")
+    B, H, W = (int(v) for v in geom)
+    M, C, ld = _rows(x)
+    _req(M == B * H * W, f"{what}: {M} rows are not the {B} x {H} x {W} pixels")
+    return B, H, W, C, ld
+
+
+def _lora_conv_rank(Cin, r, what):
+    _req(Cin % 8 == 0 and r % 4 == 0 and 4 <= r <= 64, f"{what}: Cin {Cin} % 8, rank {r} % 4 and 4 <= rank <= 64")
+
+
+def lora_conv_down(x, geom, a, out, *, scale=1.0):
+    """out[m] = scale * sum over the nine taps of x[nbr(m, tap)] @ a[:, tap]^T (az_lora_conv_down_bf16): the down product of an adapter
+    on a 3x3 / stride 1 / pad 1 convolution.  x [B H W][Cin] rows (any row stride), geom (B, H, W), a [r][3][3][Cin] contiguous (the
+    base conv weight's layout), out [B H W][r]."""
+    B, H, W, Cin, ldx = _lora_conv_geom(geom, x, "lora_conv_down x")
+    om, r, ldo = _rows(out)
+    _req(a.is_cuda and a.dtype == BF16 and a.is_contiguous() and tuple(a.shape) == (r, 3, 3, Cin) and om == B * H * W,
+         f"lora_conv_down shapes x {tuple(x.shape)} a {tuple(a.shape)} out {tuple(out.shape)}")
+    _lora_conv_rank(Cin, r, "lora_conv_down")
+    _req(ldx % 8 == 0 and ldo % 4 == 0 and x.data_ptr() % 16 == 0 and a.data_ptr() % 16 == 0 and out.data_ptr() % 8 == 0,
+         "lora_conv_down: operand alignment")
+    with _prof("lora_conv_down" + (f" {B}x{H}x{W} {Cin}->{r}" if PROFILE_SHAPES else ""), 18.0 * B * H * W * r * Cin, 2.0 * B * H * W * (Cin + r)):
+        lib().call("az_lora_conv_down_bf16", B, H, W, Cin, r, float(scale), _ptr(x), ldx, _ptr(a), _ptr(out), ldo, _stream())
+    return out
+
+
+def lora_conv_dgrad(du, geom, at, dx, *, scale=1.0):
+    """dx[m] += scale * sum over the mirrored taps of du[nbr'(m, tap)] @ at[:, tap]^T in place (az_lora_conv_dgrad_bf16).  du [B H W][r],
+    at [Cin][3][3][r] contiguous (the transposed copy of the down matrix), dx [B H W][Cin] rows (any row stride), disjoint from du."""
+    B, H, W, r, ldu = _lora_conv_geom(geom, du, "lora_conv_dgrad du")
+    xm, Cin, ldx = _rows(dx)
+    _req(at.is_cuda and at.dtype == BF16 and at.is_contiguous() and tuple(at.shape) == (Cin, 3, 3, r) and xm == B * H * W,
+         f"lora_conv_dgrad shapes du {tuple(du.shape)} at {tuple(at.shape)} dx {tuple(dx.shape)}")
+    _lora_conv_rank(Cin, r, "lora_conv_dgrad")
+    _req(ldu % 4 == 0 and ldx % 4 == 0 and du.data_ptr() % 8 == 0 and at.data_ptr() % 8 == 0 and dx.data_ptr() % 8 == 0,
+         "lora_conv_dgrad: operand alignment")
+    u0, x0 = du.data_ptr(), dx.data_ptr()
+    _req(u0 + 2 * ((xm - 1) * ldu + r) <= x0 or x0 + 2 * ((xm - 1) * ldx + Cin) <= u0, "lora_conv_dgrad: du and dx overlap")
+    with _prof("lora_conv_dgrad" + (f" {B}x{H}x{W} {Cin}<-{r}" if PROFILE_SHAPES else ""), 18.0 * B * H * W * r * Cin, 2.0 * B * H * W * (2 * Cin + r)):
+        lib().call("az_lora_conv_dgrad_bf16", B, H, W, Cin, r, float(scale), _ptr(du), ldu, _ptr(at), _ptr(dx), ldx, _stream())
+    return dx
+
+
+def lora_conv_wgrad(du, x, geom, da, *, scale=1.0, accumulate=True):
+    """da[j][tap] (+)= scale * sum over the pixels of du[m][j] * x[nbr(m, tap)] (az_lora_conv_wgrad_bf16).  du [B H W][r], x [B H W][Cin]
+    rows (any row stride), da [r][3][3][Cin] contiguous."""
+    B, H, W, Cin, ldx = _lora_conv_geom(geom, x, "lora_conv_wgrad x")
+    um, r, ldu = _rows(du)
+    _req(da.is_cuda and da.dtype == BF16 and da.is_contiguous() and tuple(da.shape) == (r, 3, 3, Cin) and um == B * H * W,
+         f"lora_conv_wgrad shapes du {tuple(du.shape)} x {tuple(x.shape)} da {tuple(da.shape)}")
+    _lora_conv_rank(Cin, r, "lora_conv_wgrad")
+    _req(ldu % 4 == 0 and ldx % 8 == 0 and du.data_ptr() % 8 == 0 and x.data_ptr() % 16 == 0, "lora_conv_wgrad: operand alignment")
+    ws = workspace(da.device)
+    ws_bytes = ws.splitk.numel() * 4 - (16 << 10)            # the last 16 KiB are the GEMM core's arrival counters
+    with _prof("lora_conv_wgrad" + (f" {B}x{H}x{W} {r}x{Cin}" if PROFILE_SHAPES else ""), 18.0 * B * H * W * r * Cin, 2.0 * B * H * W * (9 * Cin + r)):
+        lib().call("az_lora_conv_wgrad_bf16", B, H, W, Cin, r, float(scale), _ptr(du), ldu, _ptr(x), ldx, _ptr(da), int(accumulate),
+                   _ptr(ws.splitk), ws_bytes, _stream())
+    return da
+
+
 # ---------------------------------------------------------------------------------------------
 # attention
 # ---------------------------------------------------------------------------------------------

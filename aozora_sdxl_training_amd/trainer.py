@@ -196,7 +196,8 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     # reference, absent = off).  Read first: an invalid value is refused before anything is allocated.
     ema_decay, ema_warmup = _ema_options(getattr(config, _PARAMS_KEY.get(kind, "RAVEN_PARAMS"), None))
     # LORA_PARAMS (lora.options; not in the reference, absent or {} = off): rank-r adapters on the attention projections ("scope":
-    # "attention", the default) or on every Linear of every Transformer2DModel ("transformer"), the base frozen.
+    # "attention", the default), on every Linear of every Transformer2DModel ("transformer"), or on those and conv1 / conv2 /
+    # conv_shortcut of every ResnetBlock2D ("unet", with "conv_rank" / "conv_alpha" for the 3x3 ones), the base frozen.
     # Read, and what it does not combine with refused, before a UNet is loaded.
     lora_spec, lora_merged = lora_mod.options(config, world, ema_decay, unet.cfg if unet is not None else None)
     if unet is not None and getattr(unet, "lora", None) != lora_spec:
@@ -242,7 +243,9 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
             p.requires_grad = ".lora_" in n
         if rank == 0:
             n_ad = sum(p.numel() for n, p in unet.named_parameters() if ".lora_" in n)
-            print(f"INFO: LoRA is ON (rank {lora_spec.rank}, alpha {lora_spec.alpha:g}, scope {lora_spec.scope}, {len(unet.lora_state_dict()) // 2} adapted linears, {n_ad} "
+            n_conv = sum(n.endswith(".lora_A.weight") and p.dim() == 4 for n, p in unet.named_parameters())
+            convs = f" and {n_conv} adapted 3x3 convolutions at conv_rank {lora_spec.conv3_rank}, conv_alpha {lora_spec.conv3_alpha:g}" if n_conv else ""
+            print(f"INFO: LoRA is ON (rank {lora_spec.rank}, alpha {lora_spec.alpha:g}, scope {lora_spec.scope}, {len(unet.lora_state_dict()) // 2 - n_conv} adapted linears{convs}, {n_ad} "
                   f"trainable elements{', merged model saved too' if lora_merged else ''}): an option outside the reference; the base is frozen, "
                   "UNET_EXCLUDE_TARGETS is not applied, and every model file holds the adapters alone (kohya-ss layout)")
     else:

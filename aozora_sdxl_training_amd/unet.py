@@ -354,12 +354,19 @@ class AozoraUNet:
         # adapters: the backward data products of az_lora_* are NT products over transposed copies -- the adjacent down matrices of a
         # fused group as ONE stacked [parts r][K] -> [K][parts r] job (dx += du A_cat), every up matrix [N][r] -> [r][N] on its own
         # (stacked they are the [parts r][N] operand of du = s dy B)
+        # (the down matrix of a 3x3 convolution, stored [r][3][3][Cin] like its base weight, gets the base weight's kind of copy:
+        # [Cin][3][3][r], nine strided transposes -- the operand of az_lora_conv_dgrad_bf16 and of the general data-gradient kernel)
+        self._wt_conv_jobs: List[Tuple[int, int, int]] = []   # (offset, Cout, Cin)
         ltab = self._table[len(self._base_table):]
         i = 0
         while i < len(ltab):
             o, st, _ = self._slots[ltab[i][0]]
             if math.prod(st) % ALIGN:
                 raise AozoraError(f"adapter {ltab[i][0]} {st} does not fill whole {ALIGN}-element slots: stacked groups would not be adjacent")
+            if len(st) == 4:
+                self._wt_conv_jobs.append((o, st[0], st[3]))
+                i += 1
+                continue
             n = 1
             if ltab[i][0].endswith(".lora_A.weight"):
                 while i + n < len(ltab) and ltab[i + n][0].endswith(".lora_A.weight") and self._slots[ltab[i + n][0]][1] == st:
@@ -369,10 +376,9 @@ class AozoraUNet:
             self._wt_jobs.append((o, n * st[0], st[1]))
             i += n
         # 3x3 conv weights [Cout][9][Cin] -> W'[Cin][9][Cout] (nine strided transposes) for the NT-form conv dgrad
-        self._wt_conv_jobs: List[Tuple[int, int, int]] = []   # (offset, Cout, Cin)
         for name in names:
             o, st, shape = self._slots[name]
-            if name.endswith(".weight") and len(st) == 4 and st[1] == 3 and st[0] % 8 == 0 and name != "conv_in.weight":
+            if name.endswith(".weight") and len(st) == 4 and st[1] == 3 and st[0] % 8 == 0 and name != "conv_in.weight" and ".lora_" not in name:
                 self._wt_conv_jobs.append((o, st[0], st[3]))
         self._wt_dirty = True
         self._wt_version = -1
@@ -592,12 +598,12 @@ class AozoraUNet:
         return self
 
     def init_lora(self, seed: int):
-        """B = 0; A ~ U(-1/sqrt(K), 1/sqrt(K)) drawn on the CPU from one generator seeded with `seed`, in table order."""
+        """B = 0; A ~ U(-1/sqrt(K), 1/sqrt(K)) (K = the fan-in: 9 Cin for a 3x3 convolution) drawn on the CPU from one generator seeded with `seed`, in table order."""
         g = torch.Generator().manual_seed(int(seed))
         sd = {}
         for name, shape in self._table[len(self._base_table):]:
             if name.endswith(".lora_A.weight"):
-                sd[name] = (torch.rand(shape, generator=g) * 2.0 - 1.0) / math.sqrt(shape[1])
+                sd[name] = (torch.rand(shape, generator=g) * 2.0 - 1.0) / math.sqrt(math.prod(shape[1:]))
             else:
                 sd[name] = torch.zeros(shape)
         return self.load_lora_state_dict(sd)
@@ -612,18 +618,37 @@ class AozoraUNet:
         have = [(p, m) for p, m in enumerate(mods) if m + ".lora_A.weight" in self._slots]
         g = None
         if have:
-            r, n = self.lora.rank, len(have)
+            n = len(have)
             oA, stA, _ = self._slots[have[0][1] + ".lora_A.weight"]
             oB, stB, _ = self._slots[have[0][1] + ".lora_B.weight"]
-            K, N = stA[1], stB[0]
+            r, K, N = stA[0], stA[1], stB[0]        # the module's own rank (conv_rank differs from rank)
             for i, (_, m) in enumerate(have):
                 if self._slots[m + ".lora_A.weight"][0] != oA + i * r * K or self._slots[m + ".lora_B.weight"][0] != oB + i * N * r:
                     raise AozoraError(f"adapters of {mods} are not adjacent in the flat buffer")
             names = [m + sfx for _, m in have for sfx in (".lora_A.weight", ".lora_B.weight")]
             fl = lambda buf, o, rows, cols: buf[o:o + rows * cols].view(rows, cols)
-            g = SimpleNamespace(parts=[p for p, _ in have], n=n, full=n == len(mods), r=r, N=N, K=K, s=self.lora.scale, names=names,
+            g = SimpleNamespace(parts=[p for p, _ in have], n=n, full=n == len(mods), r=r, N=N, K=K, s=self.lora.scale_of(have[0][1]), names=names,
                                 A=fl(self.pflat, oA, n * r, K), GA=fl(self.gflat, oA, n * r, K), At=fl(self.wtflat, oA, K, n * r),
                                 B=fl(self.pflat, oB, n * N, r), GB=fl(self.gflat, oB, n * N, r), Bt=fl(self.wtflat, oB, n * r, N))
+        self._lora_groups[key] = g
+        return g
+
+    def _lora_conv_group(self, m):
+        """The adapter of the 3x3 convolution `m`, or None: A / GA [r][3][3][Cin] (the base weight's layout), At [Cin][3][3][r] (the
+        copy _refresh_jobs keeps), B / GB [N][r], Bt [r][N]; parts / n / full as _lora_group gives them for a single projection."""
+        key = ("conv3", m)
+        g = self._lora_groups.get(key, False)
+        if g is not False:
+            return g
+        g = None
+        if m + ".lora_A.weight" in self._slots:
+            oA, stA, _ = self._slots[m + ".lora_A.weight"]
+            oB, stB, _ = self._slots[m + ".lora_B.weight"]
+            r, K, N = stA[0], stA[3], stB[0]
+            fl = lambda buf, o, *shape: buf[o:o + math.prod(shape)].view(*shape)
+            g = SimpleNamespace(parts=[0], n=1, full=True, r=r, N=N, K=K, s=self.lora.scale_of(m), names=[m + ".lora_A.weight", m + ".lora_B.weight"],
+                                A=fl(self.pflat, oA, r, 3, 3, K), GA=fl(self.gflat, oA, r, 3, 3, K), At=fl(self.wtflat, oA, K, 3, 3, r),
+                                B=fl(self.pflat, oB, N, r), GB=fl(self.gflat, oB, N, r), Bt=fl(self.wtflat, oB, r, N))
         self._lora_groups[key] = g
         return g
 
@@ -700,6 +725,52 @@ class AozoraUNet:
                     ops.gemm(bp, sp, out[p * nb:(p + 1) * nb], trans_a=True, trans_b=False, accumulate=True, split_k=0)
         else:
             ops.lora_wgrad(small, big, out, parts=parts, scale=s, accumulate=True, small_major=small_major)
+
+    # The three gathered products of an adapter on a 3x3 convolution (conv1 / conv2 of a ResnetBlock2D).  az_conv2d_bf16 expresses
+    # each of them with Cout = r (s = 1 on all three here: the factor rides on the up product and on du; rank % 8 == 0), and the rule
+    # above decides: tools/lora_conv_time.py (profiles/lora_conv_time.json) alternated both sides at the SDXL resnet shapes, B = 4 at
+    # 1024^2, ranks 16 and 64 (adapter kernel against general kernel, us):
+    #   down   128^2 x 320: 80.2 / 70.4 (r 16), 199.5 / 75.5 (r 64)      64^2 x 640: 42.9 / 59.8, 100.9 / 60.1
+    #          32^2 x 1280: 28.4 / 113.2, 53.2 / 113.2                    32^2 x 2560: 54.4 / 221.0, 102.0 / 231.5
+    #          the adapter kernel's one pass over x wins while the grid is small; the general kernel from 65536 pixels on, and from 16384
+    #          on at rank 64 (the adapter kernel's time grows with the rank, the general kernel's does not)
+    #   dgrad  the general kernel at every measured shape (95.4 / 26.6, 431.2 / 43.5; 44.7 / 14.4, 205.8 / 21.8; 27.4 / 10.3, 111.1 / 14.9;
+    #          45.3 / 16.4, 185.1 / 25.9): nine k-steps per 16 x 16 tile with the rank padded to 32 lose to its LDS-staged tiles
+    #   wgrad  the general kernel at every measured shape (178.7 / 75.0, 320.2 / 77.8; 88.5 / 42.1, 161.5 / 46.1; 47.2 / 25.6, 85.9 / 30.1;
+    #          69.1 / 41.2, 126.1 / 44.1): the adapter kernel reads x once per tap
+    # Each rule is a tuple of (rows, rank) pairs: the general kernel is issued where pixels >= rows and rank >= rank holds for one of
+    # them -- the measured region where it won beyond the repeat spread -- and the az_lora_conv_* kernel everywhere else: below 4096
+    # pixels and below rank 16 (nothing measured), and at the ranks the general kernel cannot take (rank 4: Cout % 8).  Attributes, so that
+    # a test can reach both sides at small shapes; they choose speed, not the contract.
+    _LORA_CONV_DOWN_GEMM = ((65536, 16), (16384, 64))       # u = A (*) x
+    _LORA_CONV_DGRAD_GEMM = ((4096, 16),)                    # dx += A^T (*) du
+    _LORA_CONV_WGRAD_GEMM = ((4096, 16),)                    # dA += du^T (*) x
+
+    @staticmethod
+    def _lora_conv_general(rule, rows, r) -> bool:
+        return r % 8 == 0 and any(rows >= lo_rows and r >= lo_rank for lo_rows, lo_rank in rule)
+
+    def _lora_conv_down(self, g, x, geom, u):
+        """u = A (*) x."""
+        if self._lora_conv_general(self._LORA_CONV_DOWN_GEMM, x.shape[0], g.r):
+            ops.conv_fwd(self._as4(x, *geom), g.A, self._as4(u, *geom))
+        else:
+            ops.lora_conv_down(x, geom, g.A, u)
+
+    def _lora_conv_dgrad(self, g, du, geom, dx):
+        """dx += A^T (*) du over the transposed copy of the down matrix."""
+        if self._lora_conv_general(self._LORA_CONV_DGRAD_GEMM, du.shape[0], g.r):
+            ops.conv_dgrad_wt(self._as4(du, *geom), g.At, self._as4(dx, *geom), accumulate=True)
+        else:
+            ops.lora_conv_dgrad(du, geom, g.At, dx)
+
+    def _lora_conv_wgrad(self, g, x, geom, u, dy, du):
+        """dA += du^T (*) x; dB += s dy^T u."""
+        if self._lora_conv_general(self._LORA_CONV_WGRAD_GEMM, x.shape[0], g.r):
+            ops.conv_wgrad(self._as4(du, *geom), self._as4(x, *geom), g.GA, accumulate=True, split_k=0)
+        else:
+            ops.lora_conv_wgrad(du, x, geom, g.GA)
+        self._lora_tall(u, dy, g.GB, g.s, 1, False)
 
     def _lora_fwd(self, g, x, u, y):
         """u = x A_cat^T (x read once), then y_p += s u_p B_p^T on the column slices of the fused output."""
@@ -1132,11 +1203,24 @@ class AozoraUNet:
         ops.conv_fwd(x4, Wt, self._as4(y.t, B, Ho, Wo), stride=stride, bias=self._w[bname],
                      rowbias=rowbias.t if rowbias is not None else None,
                      residual=self._as4(residual.t, B, Ho, Wo) if residual is not None else None, upsample=upsample)
+        # the adapter of conv1 / conv2 (scope "unet") follows the base launch: it sees the base's x and adds to a y that already holds
+        # bias, the time-embedding row bias and the residual (y may be the strided half of a skip concatenation)
+        lg = None
+        if self.lora is not None and ks == 3 and stride == 1 and not upsample:
+            lg = self._lora_conv_group(wname[:-len(".weight")])
+        if lg is not None:
+            u = self._new(B * H * W_, lg.r, need_grad=False)
+            self._lora_conv_down(lg, x.t, geom, u.t)
+            self._lora_up(u.t, lg.B, y.t, lg.s)
+            l_train = self._lora_trainable(lg)
 
         def bwd():
             dy = y.g
             if dy is None:
                 return
+            if lg is not None:
+                # taken whether or not the adapter is trainable (the pool's allocation order may not depend on the freeze mask)
+                du = self._new(B * H * W_, lg.r, need_grad=False)
             dy4 = self._as4(dy, B, Ho, Wo)
             need_seg = rowbias is not None and rowbias.need_grad
             if need_seg:
@@ -1158,6 +1242,15 @@ class AozoraUNet:
             self._side_defer(wgrad)
             if need_seg:       # the time-embedding gradient is produced on the side stream and read by the chain soon: issue now
                 rowbias.ready = self._flush_side()
+            if lg is not None:
+                if x.need_grad:
+                    self._lora_du(lg, dy, du.t)
+                if l_train:
+                    def lora_wgrad():
+                        if not x.need_grad:
+                            self._lora_du(lg, dy, du.t)
+                        self._lora_conv_wgrad(lg, x.t, geom, u.t, dy, du.t)
+                    self._side_defer(lora_wgrad)
             if x.need_grad:
                 dx, add = self._gbuf(x)
                 if upsample:            # d(upsampled x) into a scratch buffer, then the 2x2 -> 1 fold into dx
@@ -1173,6 +1266,8 @@ class AozoraUNet:
                     ops.conv_dgrad_wt(dy4, wt, self._as4(dx, B, H, W_), stride=stride, accumulate=add is dx, residual=res4)
                 else:
                     ops.conv_dgrad(dy4, Wt, self._as4(dx, B, H, W_), stride=stride, cout_real=Cout, accumulate=add is dx, residual=res4)
+                if lg is not None:
+                    self._lora_conv_dgrad(lg, du.t, geom, dx)       # dx += A^T (*) du, directly behind the base data gradient
                 if cropped:
                     ops.upsample_nearest_bwd(dx.view(B, H, W_, Cin), dxs.view(B, Hs, Ws, Cin))
                 elif upsample:
@@ -1443,7 +1538,8 @@ class AozoraUNet:
             gsc = self._gw[pre + ".conv_shortcut.weight"]
             Cout, Cin = wsc.shape[0], wsc.shape[3]
             sc = self.linear(x, None, pre + ".conv_shortcut.bias",
-                             w_override=(wsc.view(Cout, Cin), gsc.view(Cout, Cin), self._trainable(pre + ".conv_shortcut.weight")))
+                             w_override=(wsc.view(Cout, Cin), gsc.view(Cout, Cin), self._trainable(pre + ".conv_shortcut.weight")),
+                             lora_mods=[pre + ".conv_shortcut"])
         else:
             sc = x
         y, _ = self.conv(n2, geom, pre + ".conv2.weight", pre + ".conv2.bias", residual=sc, out=out)

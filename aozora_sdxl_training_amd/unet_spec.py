@@ -6,7 +6,7 @@ tensors.  diffusers itself is not importable here: PARITY
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 
 @dataclass
@@ -140,19 +140,39 @@ def param_table(cfg: UNetConfig = SDXL_BASE):
 # --------------------------------------------------------------------------------------
 LORA_RANKS = (4, 8, 16, 32, 64)
 LORA_PROJECTIONS = ("to_q", "to_k", "to_v", "to_out.0")       # of attn1 and attn2 of every BasicTransformerBlock
-LORA_SCOPES = ("attention", "transformer")
+LORA_SCOPES = ("attention", "transformer", "unet")
+LORA_CONVS = ("conv1", "conv2")                               # the 3x3 convolutions of a ResnetBlock2D: conv_rank / conv_alpha
+# convolutions and linears of the UNet that scope "unet" leaves out, and why (lora_modules refuses a keyword that names one)
+LORA_UNET_REFUSED = (
+    (".time_emb_proj", "its data gradient is produced on the parameter-gradient branch and its forward is hoisted into a grouped launch"),
+    (".downsamplers.", "a stride-2 convolution"),
+    (".upsamplers.", "it reads its input through the fused nearest-2x gather"),
+    ("conv_in", "the input convolution"),
+    ("conv_out", "the output convolution"),
+)
+
+
+def lora_is_conv3(module: str) -> bool:
+    """A 3x3 convolution of a ResnetBlock2D (conv_rank / conv_alpha govern it; the 1x1 conv_shortcut is a Linear)."""
+    return module.rsplit(".", 1)[-1] in LORA_CONVS and ".resnets." in module
 
 
 @dataclass(frozen=True)
 class LoraSpec:
-    """rank-r adapters: y += (alpha / rank) (x A^T) B^T.  scope: which linears may carry one -- "attention" (the default): the eight
+    """rank-r adapters: y += (alpha / rank) (x A^T) B^T.  scope: which layers may carry one -- "attention" (the default): the eight
     attention projections of every BasicTransformerBlock; "transformer": every Linear of every Transformer2DModel (proj_in, the eight
-    projections, ff.net.0.proj, ff.net.2, proj_out: the default of the kohya-ss layout).  targets: comma-separated keywords read by
-    the freeze keywords' rule (fnmatch(name, kw if '*' in kw else '*kw*')) against the module names of the scope; '' or '*' = all."""
+    projections, ff.net.0.proj, ff.net.2, proj_out: the default of the kohya-ss layout); "unet": those and conv1, conv2 and
+    conv_shortcut of every ResnetBlock2D (kohya-ss conv_dim / conv_alpha, LoCon).  conv_rank / conv_alpha: rank and alpha of the 3x3
+    convolutions; the 1x1 conv_shortcut takes rank / alpha like a Linear.  Scope "unet" carries its conv_rank explicitly (LORA_PARAMS
+    may leave it out: lora.options puts rank there); conv_alpha None = alpha.  targets: comma-separated keywords
+    read by the freeze keywords' rule (fnmatch(name, kw if '*' in kw else '*kw*')) against the module names of the scope; '' or
+    '*' = all."""
     rank: int = 16
     alpha: float = 16.0
     targets: str = ""
     scope: str = "attention"
+    conv_rank: Optional[int] = None
+    conv_alpha: Optional[float] = None
 
     def __post_init__(self):
         if self.rank not in LORA_RANKS:
@@ -161,19 +181,62 @@ class LoraSpec:
             raise ValueError(f"LoRA alpha must be > 0, got {self.alpha!r}")
         if self.scope not in LORA_SCOPES:
             raise ValueError(f"LoRA scope {self.scope!r} is not one of {LORA_SCOPES}")
+        if self.scope == "unet" and self.conv_rank is None:
+            # a LoraSpec is resolved: lora.options fills conv_rank with rank where LORA_PARAMS leaves it out (conv_alpha may stay None = alpha)
+            raise ValueError("LoRA scope \"unet\" needs the rank of the 3x3 convolutions: LoraSpec(rank, alpha, targets, \"unet\", conv_rank)")
+        if self.conv_rank is not None and self.conv_rank not in LORA_RANKS:
+            raise ValueError(f"LoRA conv_rank {self.conv_rank!r} is not one of {LORA_RANKS}")
+        if self.conv_alpha is not None and not (float(self.conv_alpha) > 0.0):
+            raise ValueError(f"LoRA conv_alpha must be > 0, got {self.conv_alpha!r}")
+        if (self.conv_rank is not None or self.conv_alpha is not None) and self.scope != "unet":
+            raise ValueError(f"LoRA conv_rank / conv_alpha belong to scope \"unet\" (scope {self.scope!r} adapts no convolution)")
 
     @property
     def scale(self) -> float:
         return float(self.alpha) / self.rank
 
+    @property
+    def conv3_rank(self) -> int:
+        """Rank of the 3x3 convolutions: conv_rank, or rank where it is None."""
+        return self.rank if self.conv_rank is None else self.conv_rank
+
+    @property
+    def conv3_alpha(self) -> float:
+        return float(self.alpha if self.conv_alpha is None else self.conv_alpha)
+
+    def rank_of(self, module: str) -> int:
+        return self.conv3_rank if lora_is_conv3(module) else self.rank
+
+    def alpha_of(self, module: str) -> float:
+        return self.conv3_alpha if lora_is_conv3(module) else float(self.alpha)
+
+    def scale_of(self, module: str) -> float:
+        return self.alpha_of(module) / self.rank_of(module)
+
 
 def lora_modules(cfg: UNetConfig, spec: LoraSpec) -> List[str]:
-    """The adapted modules (names without '.weight') in parameter-table order.  A keyword that names a linear outside the scope, or
+    """The adapted modules (names without '.weight') in parameter-table order.  A keyword that names a layer outside the scope, or
     one that selects nothing, is refused."""
     import fnmatch
     kws = [k.strip() for k in (spec.targets or "").split(",") if k.strip()] or ["*"]
     match = lambda name, kw: fnmatch.fnmatch(name, kw if "*" in kw else f"*{kw}*")
-    linears = [n[:-7] for n, shape in param_table(cfg) if n.endswith(".weight") and len(shape) == 2]
+    table = param_table(cfg)
+    linears = [n[:-7] for n, shape in table if n.endswith(".weight") and len(shape) == 2]
+    if spec.scope == "unet":
+        resnet_conv = lambda m: ".resnets." in m and m.rsplit(".", 1)[-1] in LORA_CONVS + ("conv_shortcut",)
+        weights = [n[:-7] for n, shape in table if n.endswith(".weight") and len(shape) in (2, 4)]
+        eligible = [m for m in weights if (m in linears and ".attentions." in m) or resnet_conv(m)]
+        for kw in kws:
+            if any(match(m, kw) for m in eligible):
+                continue
+            for m in weights:
+                why = [w for key, w in LORA_UNET_REFUSED if key in m]
+                if m not in eligible and why and match(m, kw):
+                    raise ValueError(f"LoRA target {kw!r} names {m}: out of scope \"unet\" ({why[0]}); the scope adapts the Linears of "
+                                     "every Transformer2DModel and conv1, conv2, conv_shortcut of every ResnetBlock2D")
+            raise ValueError(f"LoRA target {kw!r} selects no Linear of a Transformer2DModel and no convolution of a ResnetBlock2D "
+                             "(scope \"unet\")")
+        return [m for m in eligible if any(match(m, kw) for kw in kws)]
     if spec.scope == "transformer":
         eligible = [m for m in linears if ".attentions." in m]
         for kw in kws:
@@ -199,7 +262,7 @@ def lora_table(cfg: UNetConfig, spec: LoraSpec):
     """[(name, shape)] of the adapter parameters, appended behind conv_out.bias in the parameter-table order of their modules.  Per
     attention, the down matrices A [r][in] of its fused group first (adjacent: one stacked operand), then the group's up matrices
     B [out][r], then to_out.0 (attn2: to_q first).  Every other linear of scope "transformer" (proj_in, ff.net.0.proj, ff.net.2,
-    proj_out) is A, then B, at its module's place."""
+    proj_out) is A, then B, at its module's place, and so are conv1, conv2 and conv_shortcut of scope "unet"."""
     shapes = dict(param_table(cfg))
     order = lora_modules(cfg, spec)
     mods = set(order)
@@ -215,6 +278,8 @@ def lora_table(cfg: UNetConfig, spec: LoraSpec):
             a, groups = None, [[m]]
         for g in groups:
             names = [f"{a}.{p}" for p in g if f"{a}.{p}" in mods] if a is not None else g
-            out += [(n + ".lora_A.weight", (spec.rank, shapes[n + ".weight"][1])) for n in names]
-            out += [(n + ".lora_B.weight", (shapes[n + ".weight"][0], spec.rank)) for n in names]
+            for n in names:       # a 3x3 convolution: A (r, Cin, 3, 3), stored like the base weight [r][3][3][Cin]; conv_shortcut: (r, Cin)
+                shp = shapes[n + ".weight"]
+                out.append((n + ".lora_A.weight", (spec.rank_of(n), shp[1]) + (tuple(shp[2:]) if lora_is_conv3(n) else ())))
+            out += [(n + ".lora_B.weight", (shapes[n + ".weight"][0], spec.rank_of(n))) for n in names]
     return out

@@ -578,6 +578,41 @@ int az_lora_wgrad_bf16(int M, int ns, int nb, int parts, float s, const void* S,
                        long g_part_stride, void* out, long out_stride_s, long out_stride_b, long out_part_stride, int accumulate,
                        void* workspace, long workspace_bytes, void* stream);
 
+/* ---- LoRA adapters on 3x3 convolutions (conv1 / conv2 of a ResnetBlock2D; kohya-ss conv_dim, LoCon; INTEGRATION.md "LoRA";
+ *      tests/lora_conv_ref.py restates the arithmetic in float64) ---------------------------------------------------------------
+ * For a 3x3, stride-1, pad-1 convolution with base weight W[Cout][3][3][Cin], adapters A[r][3][3][Cin] ("down", the base weight's
+ * own layout) and B[Cout][r] ("up") and s = alpha / r:
+ *     forward   u  = bf16(A (*) x)                    y  = bf16(float(y_base) + s (u B^T))            (az_lora_up_bf16)
+ *     backward  du = bf16(s (dy B))  (az_lora_down_bf16)     dx = bf16(float(dx_base) + A^T (*) du)
+ *               dA = bf16(float(dA) + du^T (*) x)            dB = bf16(float(dB) + s (dy^T u))        (az_lora_wgrad_bf16)
+ * The three gathered products are the entry points below.  Activations are NHWC rows [B H W][C] with any row stride; pixel m =
+ * (b, h, w) meets, at tap t = 3 kh + kw, pixel nbr(m, t) = (b, h + kh - 1, w + kw - 1) of the SAME image, and a tap outside the
+ * image contributes zero (a predicated zero fragment, never a load, never memory padding).  All on v_mfma_f32_16x16x32_bf16 in
+ * az_lora_*'s operand order; the rank is padded by zero fragments.  No floating-point atomics: every sum has one fixed order.
+ * Cin % 8 == 0; 4 <= r <= 64, r % 4 == 0; B H W < 2^31.  Argument errors -1130 .. -1139 (first of each entry point: geometry,
+ * Cin or r; second: a null or misaligned pointer; third: a row stride).
+ *
+ * az_lora_conv_down_bf16: out[m][n] = bf16(s sum_t sum_c X[nbr(m, t)][c] A[n][t][c]), n < r.  One pass over X per tap; the 4 waves
+ *   of a 16-pixel block split the k-range 9 Cin and are added in wave order.  X, A 16-byte aligned, ldx % 8 == 0; out 8-byte
+ *   aligned, ldo % 4 == 0; A contiguous.
+ * az_lora_conv_dgrad_bf16: dX[m][c] = bf16(float(dX[m][c]) + s sum_t sum_{j < r} dU[nbr'(m, t)][j] At[c][t][j]) with the taps
+ *   mirrored, nbr'(m, t) = (b, h - kh + 1, w - kw + 1): read-modify-write of the base data gradient with one rounding.  At is the
+ *   copy [Cin][3][3][r] of A (j contiguous per (c, t)), contiguous.  dU, At, dX 8-byte aligned, ldu % 4 == 0, ldx % 4 == 0; dU
+ *   and dX may not overlap (-1135).
+ * az_lora_conv_wgrad_bf16: dA[j][t][c] (+)= s sum_m dU[m][j] X[nbr(m, t)][c].  Two stages like az_lora_wgrad_bf16: fp32 partial
+ *   sums per row range in `workspace` (at most 64 ranges, a function of the shapes and workspace_bytes only; r * 9 Cin floats per
+ *   range, -1139 when not even one fits), then a finish in ascending order that scales, adds the previous bf16 gradient when
+ *   `accumulate` and rounds once.  dU 8-byte aligned, ldu % 4 == 0; X 16-byte aligned, ldx % 8 == 0; dA contiguous. */
+/* ref: not in the reference (train.py:2760-2761 runs the un-adapted ResnetBlock2D convolutions); follows the base convolution */
+int az_lora_conv_down_bf16(int B, int H, int W, int Cin, int r, float s, const void* X, long ldx, const void* A, void* out, long ldo,
+                           void* stream);
+/* ref: not in the reference; follows the base convolution's data gradient in the backward of train.py:2765 */
+int az_lora_conv_dgrad_bf16(int B, int H, int W, int Cin, int r, float s, const void* dU, long ldu, const void* At, void* dX, long ldx,
+                            void* stream);
+/* ref: not in the reference; stands beside the weight gradients of train.py:2765 */
+int az_lora_conv_wgrad_bf16(int B, int H, int W, int Cin, int r, float s, const void* dU, long ldu, const void* X, long ldx, void* dA,
+                            int accumulate, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- native launch tape: the executor seam (SURVEY.md 8b "az_unet_step") ----------------------------------------------------
  * The step's launch sequence is static (same entry points, pointers, streams and events every step of a resolution bucket).  The
  * host executor records it once; az_tape_play re-issues it from C: entry-point calls (arguments as 64-bit words: int / long by
