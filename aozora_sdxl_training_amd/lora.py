@@ -1,7 +1,7 @@
 """LoRA training (INTEGRATION.md "LoRA"; not in the reference, whose train.py is full fine-tuning only): the options of
 `LORA_PARAMS`, the adapter file in the kohya-ss layout that ComfyUI and A1111 load, the merged model, and the loader.  Host-side
-logic only; the arithmetic is az_lora_* (csrc/az_lora.hip) inside AozoraUNet.linear.  "scope" chooses the linears that may carry an
-adapter: the attention projections (the default), every Linear of every Transformer2DModel, or those and the convolutions of every
+logic only; the arithmetic is az_lora_* (csrc/az_lora.hip), placed by lora_exec.py for AozoraUNet.linear / conv.  "scope" chooses the
+linears that may carry an adapter: the attention projections (the default), every Linear of every Transformer2DModel, or those and the convolutions of every
 ResnetBlock2D ("unet": conv1 / conv2 at `conv_rank` / `conv_alpha`, kohya-ss conv_dim / conv_alpha; unet_spec.LoraSpec)."""
 from __future__ import annotations
 

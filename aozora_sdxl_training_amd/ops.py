@@ -38,6 +38,18 @@ def _rows(t: torch.Tensor, dtype=BF16):
     return t.shape[0], t.shape[1], t.stride(0)
 
 
+def as3(t: torch.Tensor, B, HW):
+    """[B*HW][C] row view (any row stride) -> (B,HW,C) view."""
+    ld = t.stride(0)
+    return t.as_strided((B, HW, t.shape[1]), (HW * ld, ld, 1))
+
+
+def as4(t: torch.Tensor, B, H, W_):
+    """[B*H*W][C] row view (any row stride) -> (B,H,W,C) view."""
+    ld = t.stride(0)
+    return t.as_strided((B, H, W_, t.shape[1]), (H * W_ * ld, W_ * ld, ld, 1))
+
+
 class Profiler:
     """Brackets every ABI launch with HIP events on the stream it runs on and aggregates by op class
     (bench.py uses it for the per-kernel roofline; tests never enable it)."""

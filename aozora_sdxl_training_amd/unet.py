@@ -28,6 +28,7 @@ import torch
 from . import ops
 from ._lib import lib, AozoraError, ForkEvent, Record, Wait, Live
 from .unet_spec import UNetConfig, SDXL_BASE, param_table, up_resnet_channels, LoraSpec, lora_table
+from .lora_exec import LoraAdapters, wt_jobs
 
 @dataclass
 class ExecPolicy:
@@ -229,8 +230,9 @@ class AozoraUNet:
         self.lora = lora
         self._base_table = param_table(cfg)
         self._table = self._base_table + (lora_table(cfg, lora) if lora is not None else [])
-        self._lora_groups: Dict[tuple, object] = {}
         self._layout()
+        # the adapter executor (lora_exec.py): groups, routing rules and the four per-group operations linear() / conv() call
+        self.adapters = LoraAdapters(self._slots, self.pflat, self.gflat, self.wtflat, lora.scale_of, self._trainable) if lora is not None else None
         self._pools: Dict[tuple, _Pool] = {}
         self._pool: Optional[_Pool] = None
         self._arenas: Dict[int, _Arena] = {}     # parity -> the arena its pools share (survives _pools.clear())
@@ -351,30 +353,9 @@ class AozoraUNet:
                 rows *= 2
                 skip.add(name.replace("to_k", "to_v"))
             self._wt_jobs.append((o, rows, cols))
-        # adapters: the backward data products of az_lora_* are NT products over transposed copies -- the adjacent down matrices of a
-        # fused group as ONE stacked [parts r][K] -> [K][parts r] job (dx += du A_cat), every up matrix [N][r] -> [r][N] on its own
-        # (stacked they are the [parts r][N] operand of du = s dy B)
-        # (the down matrix of a 3x3 convolution, stored [r][3][3][Cin] like its base weight, gets the base weight's kind of copy:
-        # [Cin][3][3][r], nine strided transposes -- the operand of az_lora_conv_dgrad_bf16 and of the general data-gradient kernel)
-        self._wt_conv_jobs: List[Tuple[int, int, int]] = []   # (offset, Cout, Cin)
-        ltab = self._table[len(self._base_table):]
-        i = 0
-        while i < len(ltab):
-            o, st, _ = self._slots[ltab[i][0]]
-            if math.prod(st) % ALIGN:
-                raise AozoraError(f"adapter {ltab[i][0]} {st} does not fill whole {ALIGN}-element slots: stacked groups would not be adjacent")
-            if len(st) == 4:
-                self._wt_conv_jobs.append((o, st[0], st[3]))
-                i += 1
-                continue
-            n = 1
-            if ltab[i][0].endswith(".lora_A.weight"):
-                while i + n < len(ltab) and ltab[i + n][0].endswith(".lora_A.weight") and self._slots[ltab[i + n][0]][1] == st:
-                    n += 1
-                if n > 3:
-                    raise AozoraError(f"{n} adjacent down matrices from {ltab[i][0]} on: a fused group has at most 3 parts")
-            self._wt_jobs.append((o, n * st[0], st[1]))
-            i += n
+        # adapters (lora_exec.wt_jobs): their linear jobs behind the base linear jobs, their 3x3 jobs in front of the base 3x3 jobs
+        lin, self._wt_conv_jobs = wt_jobs(self._table[len(self._base_table):], self._slots)      # (offset, Cout, Cin)
+        self._wt_jobs += lin
         # 3x3 conv weights [Cout][9][Cin] -> W'[Cin][9][Cout] (nine strided transposes) for the NT-form conv dgrad
         for name in names:
             o, st, shape = self._slots[name]
@@ -607,187 +588,6 @@ class AozoraUNet:
             else:
                 sd[name] = torch.zeros(shape)
         return self.load_lora_state_dict(sd)
-
-    def _lora_group(self, mods):
-        """The adapters of the projections `mods` (one linear() call: a single projection or the parts of a fused one), or None.
-        Stacked views: A [n r][K] / At [K][n r] (the n adapted parts side by side), B [n N][r] / Bt [n r][N]."""
-        key = tuple(mods)
-        g = self._lora_groups.get(key, False)
-        if g is not False:
-            return g
-        have = [(p, m) for p, m in enumerate(mods) if m + ".lora_A.weight" in self._slots]
-        g = None
-        if have:
-            n = len(have)
-            oA, stA, _ = self._slots[have[0][1] + ".lora_A.weight"]
-            oB, stB, _ = self._slots[have[0][1] + ".lora_B.weight"]
-            r, K, N = stA[0], stA[1], stB[0]        # the module's own rank (conv_rank differs from rank)
-            for i, (_, m) in enumerate(have):
-                if self._slots[m + ".lora_A.weight"][0] != oA + i * r * K or self._slots[m + ".lora_B.weight"][0] != oB + i * N * r:
-                    raise AozoraError(f"adapters of {mods} are not adjacent in the flat buffer")
-            names = [m + sfx for _, m in have for sfx in (".lora_A.weight", ".lora_B.weight")]
-            fl = lambda buf, o, rows, cols: buf[o:o + rows * cols].view(rows, cols)
-            g = SimpleNamespace(parts=[p for p, _ in have], n=n, full=n == len(mods), r=r, N=N, K=K, s=self.lora.scale_of(have[0][1]), names=names,
-                                A=fl(self.pflat, oA, n * r, K), GA=fl(self.gflat, oA, n * r, K), At=fl(self.wtflat, oA, K, n * r),
-                                B=fl(self.pflat, oB, n * N, r), GB=fl(self.gflat, oB, n * N, r), Bt=fl(self.wtflat, oB, n * r, N))
-        self._lora_groups[key] = g
-        return g
-
-    def _lora_conv_group(self, m):
-        """The adapter of the 3x3 convolution `m`, or None: A / GA [r][3][3][Cin] (the base weight's layout), At [Cin][3][3][r] (the
-        copy _refresh_jobs keeps), B / GB [N][r], Bt [r][N]; parts / n / full as _lora_group gives them for a single projection."""
-        key = ("conv3", m)
-        g = self._lora_groups.get(key, False)
-        if g is not False:
-            return g
-        g = None
-        if m + ".lora_A.weight" in self._slots:
-            oA, stA, _ = self._slots[m + ".lora_A.weight"]
-            oB, stB, _ = self._slots[m + ".lora_B.weight"]
-            r, K, N = stA[0], stA[3], stB[0]
-            fl = lambda buf, o, *shape: buf[o:o + math.prod(shape)].view(*shape)
-            g = SimpleNamespace(parts=[0], n=1, full=True, r=r, N=N, K=K, s=self.lora.scale_of(m), names=[m + ".lora_A.weight", m + ".lora_B.weight"],
-                                A=fl(self.pflat, oA, r, 3, 3, K), GA=fl(self.gflat, oA, r, 3, 3, K), At=fl(self.wtflat, oA, K, 3, 3, r),
-                                B=fl(self.pflat, oB, N, r), GB=fl(self.gflat, oB, N, r), Bt=fl(self.wtflat, oB, r, N))
-        self._lora_groups[key] = g
-        return g
-
-    def _lora_trainable(self, g) -> bool:
-        return g is not None and any(self._trainable(n) for n in g.names)
-
-    def _lora_parts(self, g):
-        """(index in the stack, column part of the fused output, number of parts) per launch: one launch for a whole group."""
-        return [(0, 0, g.n)] if g.full else [(i, p, 1) for i, p in enumerate(g.parts)]
-
-    # Which kernel carries an adapter product follows tools/lora_time.py (profiles/lora_time.json): an az_lora_* kernel is used where it
-    # beats az_gemm_bf16 beyond the repeat spread, or where the general product cannot express the contract -- a factor s != 1, a small
-    # dimension that is no multiple of 8 (rank 4 and its 8-byte slices), `du` of several parts with s.  Everywhere else the general
-    # product in its accumulate form computes the same contract:
-    #   down   az_lora_down_bf16, except many rows at a stacked rank >= 64 (M = 16384, r = 64: 13.3 against 9.2 us)
-    #   up     az_gemm_bf16, except few rows at rank <= 32 (the text context: 5.2 against 7.3 us) and a fused q|k|v group of rank <= 16
-    #          at up to 4096 rows in ONE launch (22.2 against 25.6 us for three general products)
-    #   tall   az_gemm_bf16 (the adapter kernel loses at every shape: 24.1 against 15.5 us)
-    #   up + GEGLU (ff.net.0.proj; profiles/lora_ff_time.json)  az_lora_up_geglu_bf16 where the up product alone would be az_lora_up_bf16:
-    #          against that kernel + az_geglu_fwd it wins beyond the spread (M = 4096, H = 5120: 65.2 against 69.2 us at rank 16, 120.9
-    #          against 123.2 at rank 64; M = 16384, H = 2560, rank 16: 125.7 against 134.7), except many rows at rank 64, where two
-    #          MI355X disagreed (233.7 against 241.5 us on one, 251.3 against 244.0 on the other): the two-launch form there.  Where the
-    #          up product is the general product (s = 1, rank % 8 == 0, many rows) the fused kernel loses to it + az_geglu_fwd (65.3
-    #          against 56.2, 120.4 against 55.6, 125.5 against 101.4, 233.2 against 108.7 us): the two-launch form there too
-    # The thresholds are attributes so that a test can reach both sides at small shapes; they choose speed, not the contract (the fp32
-    # summation order differs between the two kernels).
-    _LORA_DOWN_GEMM_ROWS, _LORA_DOWN_GEMM_RANK = 8192, 64
-    _LORA_UP_FEW_ROWS, _LORA_UP_FEW_RANK = 512, 32
-    _LORA_UP_FUSED_ROWS, _LORA_UP_FUSED_RANK = 4096, 16
-    _LORA_UP_GEGLU_ROWS, _LORA_UP_GEGLU_RANK = 8192, 64
-
-    def _lora_down(self, x, w, out):
-        """out = x w^T (the stacked down matrices: x is read once)."""
-        R = w.shape[0]
-        if R % 8 == 0 and R >= self._LORA_DOWN_GEMM_RANK and x.shape[0] >= self._LORA_DOWN_GEMM_ROWS:
-            ops.gemm(x, w, out, trans_b=True)
-        else:
-            ops.lora_down(x, w, out)
-
-    def _lora_up_own(self, rows, r, s, parts=1) -> bool:
-        """The up product goes to az_lora_up_bf16 (True) or to az_gemm_bf16 in its accumulate form (False)."""
-        return (s != 1.0 or r % 8 != 0 or (rows <= self._LORA_UP_FEW_ROWS and r <= self._LORA_UP_FEW_RANK)
-                or (parts == 3 and rows <= self._LORA_UP_FUSED_ROWS and r <= self._LORA_UP_FUSED_RANK))
-
-    def _lora_up(self, u, w, y, s, parts=1):
-        """y_p += s u_p w_p^T for the `parts` stacked parts."""
-        r, N, rows = w.shape[1], w.shape[0] // parts, u.shape[0]
-        if self._lora_up_own(rows, r, s, parts):
-            ops.lora_up(u, w, y, parts=parts, scale=s)
-            return
-        for p in range(parts):
-            ops.gemm(u[:, p * r:(p + 1) * r], w[p * N:(p + 1) * N], y[:, p * N:(p + 1) * N], trans_b=True, accumulate=True)
-
-    def _lora_up_geglu(self, u, w, proj, out, s):
-        """proj += s u w^T, then out = GEGLU(proj): az_lora_up_geglu_bf16 (one launch, proj read once) wherever _lora_up would take
-        az_lora_up_bf16, else the two-launch form (the general product, then az_geglu_fwd)."""
-        rows, r = u.shape[0], w.shape[1]
-        if self._lora_up_own(rows, r, s) and not (rows >= self._LORA_UP_GEGLU_ROWS and r >= self._LORA_UP_GEGLU_RANK):
-            ops.lora_up_geglu(u, w, proj, out, scale=s)
-        else:
-            self._lora_up(u, w, proj, s)
-            ops.geglu_fwd(proj, out)
-
-    @staticmethod
-    def _lora_tall(small, big, out, s, parts, small_major):
-        """out_p += s small_p^T big_p; out_p [ns][nb] (small_major) or [nb][ns]."""
-        ns, nb = small.shape[1] // parts, big.shape[1] // parts
-        if s == 1.0 and ns % 8 == 0:
-            for p in range(parts):
-                sp, bp = small[:, p * ns:(p + 1) * ns], big[:, p * nb:(p + 1) * nb]
-                if small_major:
-                    ops.gemm(sp, bp, out[p * ns:(p + 1) * ns], trans_a=True, trans_b=False, accumulate=True, split_k=0)
-                else:
-                    ops.gemm(bp, sp, out[p * nb:(p + 1) * nb], trans_a=True, trans_b=False, accumulate=True, split_k=0)
-        else:
-            ops.lora_wgrad(small, big, out, parts=parts, scale=s, accumulate=True, small_major=small_major)
-
-    # The three gathered products of an adapter on a 3x3 convolution (conv1 / conv2 of a ResnetBlock2D).  az_conv2d_bf16 expresses
-    # each of them with Cout = r (s = 1 on all three here: the factor rides on the up product and on du; rank % 8 == 0), and the rule
-    # above decides: tools/lora_conv_time.py (profiles/lora_conv_time.json) alternated both sides at the SDXL resnet shapes, B = 4 at
-    # 1024^2, ranks 16 and 64 (adapter kernel against general kernel, us):
-    #   down   128^2 x 320: 80.2 / 70.4 (r 16), 199.5 / 75.5 (r 64)      64^2 x 640: 42.9 / 59.8, 100.9 / 60.1
-    #          32^2 x 1280: 28.4 / 113.2, 53.2 / 113.2                    32^2 x 2560: 54.4 / 221.0, 102.0 / 231.5
-    #          the adapter kernel's one pass over x wins while the grid is small; the general kernel from 65536 pixels on, and from 16384
-    #          on at rank 64 (the adapter kernel's time grows with the rank, the general kernel's does not)
-    #   dgrad  the general kernel at every measured shape (95.4 / 26.6, 431.2 / 43.5; 44.7 / 14.4, 205.8 / 21.8; 27.4 / 10.3, 111.1 / 14.9;
-    #          45.3 / 16.4, 185.1 / 25.9): nine k-steps per 16 x 16 tile with the rank padded to 32 lose to its LDS-staged tiles
-    #   wgrad  the general kernel at every measured shape (178.7 / 75.0, 320.2 / 77.8; 88.5 / 42.1, 161.5 / 46.1; 47.2 / 25.6, 85.9 / 30.1;
-    #          69.1 / 41.2, 126.1 / 44.1): the adapter kernel reads x once per tap
-    # Each rule is a tuple of (rows, rank) pairs: the general kernel is issued where pixels >= rows and rank >= rank holds for one of
-    # them -- the measured region where it won beyond the repeat spread -- and the az_lora_conv_* kernel everywhere else: below 4096
-    # pixels and below rank 16 (nothing measured), and at the ranks the general kernel cannot take (rank 4: Cout % 8).  Attributes, so that
-    # a test can reach both sides at small shapes; they choose speed, not the contract.
-    _LORA_CONV_DOWN_GEMM = ((65536, 16), (16384, 64))       # u = A (*) x
-    _LORA_CONV_DGRAD_GEMM = ((4096, 16),)                    # dx += A^T (*) du
-    _LORA_CONV_WGRAD_GEMM = ((4096, 16),)                    # dA += du^T (*) x
-
-    @staticmethod
-    def _lora_conv_general(rule, rows, r) -> bool:
-        return r % 8 == 0 and any(rows >= lo_rows and r >= lo_rank for lo_rows, lo_rank in rule)
-
-    def _lora_conv_down(self, g, x, geom, u):
-        """u = A (*) x."""
-        if self._lora_conv_general(self._LORA_CONV_DOWN_GEMM, x.shape[0], g.r):
-            ops.conv_fwd(self._as4(x, *geom), g.A, self._as4(u, *geom))
-        else:
-            ops.lora_conv_down(x, geom, g.A, u)
-
-    def _lora_conv_dgrad(self, g, du, geom, dx):
-        """dx += A^T (*) du over the transposed copy of the down matrix."""
-        if self._lora_conv_general(self._LORA_CONV_DGRAD_GEMM, du.shape[0], g.r):
-            ops.conv_dgrad_wt(self._as4(du, *geom), g.At, self._as4(dx, *geom), accumulate=True)
-        else:
-            ops.lora_conv_dgrad(du, geom, g.At, dx)
-
-    def _lora_conv_wgrad(self, g, x, geom, u, dy, du):
-        """dA += du^T (*) x; dB += s dy^T u."""
-        if self._lora_conv_general(self._LORA_CONV_WGRAD_GEMM, x.shape[0], g.r):
-            ops.conv_wgrad(self._as4(du, *geom), self._as4(x, *geom), g.GA, accumulate=True, split_k=0)
-        else:
-            ops.lora_conv_wgrad(du, x, geom, g.GA)
-        self._lora_tall(u, dy, g.GB, g.s, 1, False)
-
-    def _lora_fwd(self, g, x, u, y):
-        """u = x A_cat^T (x read once), then y_p += s u_p B_p^T on the column slices of the fused output."""
-        self._lora_down(x, g.A, u)
-        for i, p, n in self._lora_parts(g):
-            self._lora_up(u[:, i * g.r:(i + n) * g.r], g.B[i * g.N:(i + n) * g.N], y[:, p * g.N:(p + n) * g.N], g.s, n)
-
-    def _lora_du(self, g, dy, du):
-        """du_p = s dy_p B_p over the transposed copies of the up matrices."""
-        for i, p, n in self._lora_parts(g):
-            ops.lora_down(dy[:, p * g.N:(p + n) * g.N], g.Bt[i * g.r:(i + n) * g.r], du[:, i * g.r:(i + n) * g.r], parts=n, scale=g.s)
-
-    def _lora_wgrad(self, g, x, u, dy, du):
-        """dA_cat += du^T x; dB_p += s dy_p^T u_p."""
-        self._lora_tall(du, x, g.GA, 1.0, 1, True)
-        for i, p, n in self._lora_parts(g):
-            self._lora_tall(u[:, i * g.r:(i + n) * g.r], dy[:, p * g.N:(p + n) * g.N], g.GB[i * g.N:(i + n) * g.N], g.s, n, False)
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict=True):
         with torch.no_grad():
@@ -1056,6 +856,31 @@ class AozoraUNet:
             return
         ops.colsum_grad(dy, rps, seg_out.g.view(-1) if seg_out is not None else None, bias, n_real)
 
+    # ---- the adapter of a layer (lora_exec.LoraGroup `lg`): linear() and conv() place its launches through these three
+    def _adapter_fwd(self, lg, x: Act, y: Act, geom=None, geglu_out: Optional[Act] = None):
+        """The adapter follows the base product: u is taken from the pool behind y.  -> (u, whether the adapter is trainable)."""
+        u = self._new(x.t.shape[0], lg.n * lg.r, need_grad=False)
+        self.adapters.fwd(lg, x.t, u.t, y.t, geom, geglu_out.t if geglu_out is not None else None)
+        return u, self.adapters.trainable(lg)
+
+    def _adapter_du_buf(self, lg, x: Act) -> Optional[Act]:
+        """du, first thing in a bwd(): whether or not the adapter is trainable (the pool's allocation order may not depend on the freeze mask)."""
+        return self._new(x.t.shape[0], lg.n * lg.r, need_grad=False) if lg is not None else None
+
+    def _adapter_bwd(self, lg, l_train, x: Act, u: Act, dy, du: Act, geom=None):
+        """Behind the base layer's weight gradient, in front of its data gradient: du on the chain if the input has a gradient, and the
+        adapter's weight gradients on the branch.  (The layer adds adapters.dgrad to dx itself, directly behind its own data gradient.)"""
+        if x.need_grad:
+            self.adapters.du(lg, dy, du.t)
+        if l_train:
+            def wgrad():
+                # without an input gradient (the text context) nothing on the chain reads du, and dy may itself be produced on the
+                # branch (the dK | dV kernel of a cross-attention): du then runs there too, in order behind its producer
+                if not x.need_grad:
+                    self.adapters.du(lg, dy, du.t)
+                self.adapters.wgrad(lg, x.t, u.t, dy, du.t, geom)
+            self._side_defer(wgrad)
+
     def linear(self, x: Act, wname: str, bname: Optional[str], residual: Optional[Act] = None,
                w_override: Optional[Tuple[torch.Tensor, torch.Tensor, bool]] = None, out: Optional[Act] = None,
                pre: Optional[Act] = None, side_dgrad: bool = False, geglu_out: Optional[Act] = None,
@@ -1078,8 +903,8 @@ class AozoraUNet:
         WT = self._wt(W) if x.need_grad else None
         rows = x.t.shape[0]
         lg = None
-        if self.lora is not None:
-            lg = self._lora_group(lora_mods if lora_mods is not None else ([wname[:-len(".weight")]] if wname else []))
+        if self.adapters is not None:
+            lg = self.adapters.group(lora_mods if lora_mods is not None else ([wname[:-len(".weight")]] if wname else []))
         if pre is not None:
             y = pre
         else:
@@ -1088,26 +913,18 @@ class AozoraUNet:
                 ops.gemm_geglu_fwd(x.t, W, self._w[bname] if bname else None, y.t, geglu_out.t)
             else:
                 # few-row products (the K/V projections of the 77-token context: 48 tiles) split along k to cover more CUs
-                # (an adapted GEGLU projection: the plain product -- the GEGLU follows the adapter, in _lora_up_geglu)
+                # (an adapted GEGLU projection: the plain product -- the GEGLU follows the adapter, in LoraRoutes.up_geglu)
                 ops.gemm(x.t, W, y.t, trans_b=True, bias=self._w[bname] if bname else None,
                          residual=residual.t if residual is not None else None,
                          split_k=0 if (rows <= 512 and residual is None) else 1)
         if lg is not None:      # the adapter follows the base product (a hoisted one: here, at the layer's own place on the tape)
-            u = self._new(rows, lg.n * lg.r, need_grad=False)
-            if geglu_out is not None:
-                self._lora_down(x.t, lg.A, u.t)
-                self._lora_up_geglu(u.t, lg.B, y.t, geglu_out.t, lg.s)
-            else:
-                self._lora_fwd(lg, x.t, u.t, y.t)
-            l_train = self._lora_trainable(lg)
+            u, l_train = self._adapter_fwd(lg, x, y, geglu_out=geglu_out)
 
         def bwd():
             dy = y.g
             if dy is None:
                 return
-            if lg is not None:
-                # taken whether or not the adapter is trainable (the pool's allocation order may not depend on the freeze mask)
-                du = self._new(rows, lg.n * lg.r, need_grad=False)
+            du = self._adapter_du_buf(lg, x)
             on_side = side_dgrad and self.policy.temb_side and self.concurrent_wgrad and len(self._sides) == 1
             if on_side:
                 y.ready = None      # written on the branch, read on the branch
@@ -1133,16 +950,7 @@ class AozoraUNet:
             elif w_train or b_train:
                 self._side_defer(wgrad)
             if lg is not None:
-                if x.need_grad:
-                    self._lora_du(lg, dy, du.t)
-                if l_train:
-                    def lora_wgrad():
-                        # without an input gradient (the text context) nothing on the chain reads du, and dy may itself be produced on the
-                        # branch (the dK | dV kernel of a cross-attention): du then runs there too, in order behind its producer
-                        if not x.need_grad:
-                            self._lora_du(lg, dy, du.t)
-                        self._lora_wgrad(lg, x.t, u.t, dy, du.t)
-                    self._side_defer(lora_wgrad)
+                self._adapter_bwd(lg, l_train, x, u, dy, du)
             if x.need_grad:
                 dx, add = self._gbuf(x)
                 oop = add is not None and add is not dx
@@ -1151,7 +959,7 @@ class AozoraUNet:
                     ops.gemm(dy, WT, dx, trans_b=True, accumulate=add is dx, residual=add if oop else None,      # dX = dY . W  as  dY . (W^T)^T
                              split_k=0 if (rows <= 512 and not oop) else 1)
                     if lg is not None:
-                        self._lora_up(du.t, lg.At, dx, 1.0)         # dx += du A_cat, directly behind the base product
+                        self.adapters.dgrad(lg, du.t, dx)         # dx += du A_cat, directly behind the base product
                 if on_side:
                     self._side_defer(dgrad)
                     x.ready = self._flush_side()
@@ -1161,18 +969,6 @@ class AozoraUNet:
                 self._give_grad(residual, dy)
         self._tape.append(bwd)
         return y
-
-    @staticmethod
-    def _as3(t: torch.Tensor, B, HW):
-        """[B*HW][C] row view (any row stride) -> (B,HW,C) view."""
-        ld = t.stride(0)
-        return t.as_strided((B, HW, t.shape[1]), (HW * ld, ld, 1))
-
-    @staticmethod
-    def _as4(t: torch.Tensor, B, H, W_):
-        """[B*H*W][C] row view (any row stride) -> (B,H,W,C) view."""
-        ld = t.stride(0)
-        return t.as_strided((B, H, W_, t.shape[1]), (H * W_ * ld, W_ * ld, ld, 1))
 
     def conv(self, x: Act, geom, wname, bname, stride=1, rowbias: Optional[Act] = None, residual: Optional[Act] = None,
              upsample=False, out: Optional[Act] = None, up_to: Optional[Tuple[int, int]] = None) -> Tuple[Act, tuple]:
@@ -1199,29 +995,24 @@ class AozoraUNet:
         y = out if out is not None else self._new(B * Ho * Wo, Cout)      # out: a [rows][Cout] view with any row stride (one half of a skip concat)
         if tuple(y.t.shape) != (B * Ho * Wo, Cout):
             raise AozoraError("conv destination shape")
-        x4 = self._as4(x.t, B, Hs, Ws)
-        ops.conv_fwd(x4, Wt, self._as4(y.t, B, Ho, Wo), stride=stride, bias=self._w[bname],
+        x4 = ops.as4(x.t, B, Hs, Ws)
+        ops.conv_fwd(x4, Wt, ops.as4(y.t, B, Ho, Wo), stride=stride, bias=self._w[bname],
                      rowbias=rowbias.t if rowbias is not None else None,
-                     residual=self._as4(residual.t, B, Ho, Wo) if residual is not None else None, upsample=upsample)
+                     residual=ops.as4(residual.t, B, Ho, Wo) if residual is not None else None, upsample=upsample)
         # the adapter of conv1 / conv2 (scope "unet") follows the base launch: it sees the base's x and adds to a y that already holds
         # bias, the time-embedding row bias and the residual (y may be the strided half of a skip concatenation)
         lg = None
-        if self.lora is not None and ks == 3 and stride == 1 and not upsample:
-            lg = self._lora_conv_group(wname[:-len(".weight")])
+        if self.adapters is not None and ks == 3 and stride == 1 and not upsample:
+            lg = self.adapters.group([wname[:-len(".weight")]], conv3=True)
         if lg is not None:
-            u = self._new(B * H * W_, lg.r, need_grad=False)
-            self._lora_conv_down(lg, x.t, geom, u.t)
-            self._lora_up(u.t, lg.B, y.t, lg.s)
-            l_train = self._lora_trainable(lg)
+            u, l_train = self._adapter_fwd(lg, x, y, geom=geom)
 
         def bwd():
             dy = y.g
             if dy is None:
                 return
-            if lg is not None:
-                # taken whether or not the adapter is trainable (the pool's allocation order may not depend on the freeze mask)
-                du = self._new(B * H * W_, lg.r, need_grad=False)
-            dy4 = self._as4(dy, B, Ho, Wo)
+            du = self._adapter_du_buf(lg, x)
+            dy4 = ops.as4(dy, B, Ho, Wo)
             need_seg = rowbias is not None and rowbias.need_grad
             if need_seg:
                 self._gbuf_single(rowbias, "segment-sum target")      # allocate on the main path (pool order is stream-agnostic)
@@ -1243,14 +1034,7 @@ class AozoraUNet:
             if need_seg:       # the time-embedding gradient is produced on the side stream and read by the chain soon: issue now
                 rowbias.ready = self._flush_side()
             if lg is not None:
-                if x.need_grad:
-                    self._lora_du(lg, dy, du.t)
-                if l_train:
-                    def lora_wgrad():
-                        if not x.need_grad:
-                            self._lora_du(lg, dy, du.t)
-                        self._lora_conv_wgrad(lg, x.t, geom, u.t, dy, du.t)
-                    self._side_defer(lora_wgrad)
+                self._adapter_bwd(lg, l_train, x, u, dy, du, geom)
             if x.need_grad:
                 dx, add = self._gbuf(x)
                 if upsample:            # d(upsampled x) into a scratch buffer, then the 2x2 -> 1 fold into dx
@@ -1259,15 +1043,15 @@ class AozoraUNet:
                     dxs = dx
                     dx = self._pool.get((B * H * W_, Cin), BF16)
                 oop = add is not None and add is not dx
-                res4 = self._as4(add, B, H, W_) if oop else None
+                res4 = ops.as4(add, B, H, W_) if oop else None
                 if Cout % 8 == 0 and dy.shape[1] == Cout:
                     o_w = (Wt.data_ptr() - self.pflat.data_ptr()) // 2
                     wt = self.wtflat[o_w:o_w + Wt.numel()].view(Cin, 3, 3, Cout)
-                    ops.conv_dgrad_wt(dy4, wt, self._as4(dx, B, H, W_), stride=stride, accumulate=add is dx, residual=res4)
+                    ops.conv_dgrad_wt(dy4, wt, ops.as4(dx, B, H, W_), stride=stride, accumulate=add is dx, residual=res4)
                 else:
-                    ops.conv_dgrad(dy4, Wt, self._as4(dx, B, H, W_), stride=stride, cout_real=Cout, accumulate=add is dx, residual=res4)
+                    ops.conv_dgrad(dy4, Wt, ops.as4(dx, B, H, W_), stride=stride, cout_real=Cout, accumulate=add is dx, residual=res4)
                 if lg is not None:
-                    self._lora_conv_dgrad(lg, du.t, geom, dx)       # dx += A^T (*) du, directly behind the base data gradient
+                    self.adapters.dgrad(lg, du.t, dx, geom)       # dx += A^T (*) du, directly behind the base data gradient
                 if cropped:
                     ops.upsample_nearest_bwd(dx.view(B, H, W_, Cin), dxs.view(B, Hs, Ws, Cin))
                 elif upsample:
@@ -1284,7 +1068,7 @@ class AozoraUNet:
         y = self._new(B * H * W_, C)
         stats = self._pool.get((B * G * 2,), F32)
         gam, bet = self._w[prefix + ".weight"], self._w[prefix + ".bias"]
-        x3 = self._as3(x.t, B, H * W_)
+        x3 = ops.as3(x.t, B, H * W_)
         ops.groupnorm_fwd(x3, gam, bet, y.t.view(B, H * W_, C), stats, G, eps, silu)
 
         def bwd():
@@ -1292,13 +1076,13 @@ class AozoraUNet:
             if dy is None:
                 return
             tg, tb = self._trainable(prefix + ".weight"), self._trainable(prefix + ".bias")
-            dy3 = self._as3(dy, B, H * W_)
+            dy3 = ops.as3(dy, B, H * W_)
             dx3, add3 = None, None
             if x.need_grad:
                 dx, add = self._gbuf(x)
-                dx3 = self._as3(dx, B, H * W_)
+                dx3 = ops.as3(dx, B, H * W_)
                 if add is not None:
-                    add3 = self._as3(add, B, H * W_)
+                    add3 = ops.as3(add, B, H * W_)
             ops.groupnorm_bwd(x3, gam, bet, stats, dy3, dx3, self._gw[prefix + ".weight"] if tg else None,
                               self._gw[prefix + ".bias"] if tb else None, G, silu, dx_add=add3)
         self._tape.append(bwd)
@@ -1384,7 +1168,7 @@ class AozoraUNet:
             q = self.linear(x, prefix + ".to_q.weight", None)
             kv_w = self._fused_w([prefix + ".to_k.weight", prefix + ".to_v.weight"])
             kv_mods = [prefix + ".to_k", prefix + ".to_v"]
-            kv_train = kv_w[2] or (self.lora is not None and self._lora_trainable(self._lora_group(kv_mods)))
+            kv_train = kv_w[2] or (self.adapters is not None and self.adapters.trainable(self.adapters.group(kv_mods)))
             kv = self.linear(ctx, None, None, w_override=kv_w, pre=self._hoisted.pop(prefix + ".kv", None), lora_mods=kv_mods)
             q3 = q.t.view(B, T, C)
             k3 = kv.t.view(B, ctx_len, 2 * C)[..., :C]

@@ -148,15 +148,15 @@ def test_general_convolution_side_matches_the_oracle_and_is_recorded(setup, monk
     _gauss_b(unet0)
     ours, _ = _recorded(lambda: _micro(unet0, dev))
     unet = _unet(setup, spec)
-    unet._LORA_CONV_DOWN_GEMM = unet._LORA_CONV_DGRAD_GEMM = unet._LORA_CONV_WGRAD_GEMM = ((0, 0),)
+    unet.adapters.routes.CONV_DOWN_GEMM = unet.adapters.routes.CONV_DGRAD_GEMM = unet.adapters.routes.CONV_WGRAD_GEMM = ((0, 0),)
     names, _ = _recorded(lambda: _parity(monkeypatch, unet, spec, params, oc, pc))
     assert all(ours.count(e) == 2 * RESNETS and names.count(e) == 0 for e in CONV_ENTRIES)
     assert names.count("az_conv2d_bf16") == ours.count("az_conv2d_bf16") + 3 * 2 * RESNETS
     one = _unet(setup, spec)
-    one._LORA_CONV_DGRAD_GEMM = ((0, 0),)          # each rule moves its own product only
+    one.adapters.routes.CONV_DGRAD_GEMM = ((0, 0),)          # each rule moves its own product only
     names, _ = _recorded(lambda: _micro(one, dev))
     assert [names.count(e) for e in CONV_ENTRIES] == [2 * RESNETS, 0, 2 * RESNETS]
-    one._LORA_CONV_DGRAD_GEMM = ((0, 16),)         # ... from its rank on: conv_rank 8 stays with the adapter kernel
+    one.adapters.routes.CONV_DGRAD_GEMM = ((0, 16),)         # ... from its rank on: conv_rank 8 stays with the adapter kernel
     names, _ = _recorded(lambda: _micro(one, dev))
     assert [names.count(e) for e in CONV_ENTRIES] == [2 * RESNETS] * 3
 
@@ -166,7 +166,7 @@ def test_rank_4_stays_with_the_adapter_kernels(setup):
     from aozora_sdxl_training_amd.unet_spec import LoraSpec
     pc, oc, params, base, _, _ = setup
     unet = _unet(setup, LoraSpec(8, 8.0, "resnets", "unet", 4, 4.0))
-    unet._LORA_CONV_DOWN_GEMM = unet._LORA_CONV_DGRAD_GEMM = unet._LORA_CONV_WGRAD_GEMM = ((0, 0),)
+    unet.adapters.routes.CONV_DOWN_GEMM = unet.adapters.routes.CONV_DGRAD_GEMM = unet.adapters.routes.CONV_WGRAD_GEMM = ((0, 0),)
     _gauss_b(unet)
     names, _ = _recorded(lambda: _micro(unet, _args(pc)[1]))
     assert all(names.count(e) == 2 * RESNETS for e in CONV_ENTRIES)

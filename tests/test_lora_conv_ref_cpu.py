@@ -174,20 +174,20 @@ def test_other_scopes_give_the_tables_they_gave():
 
 
 def test_shipped_kernel_rules_follow_the_measured_table():
-    """AozoraUNet._LORA_CONV_*_GEMM issue the general convolution exactly where profiles/lora_conv_time.json has it winning beyond the
+    """lora_exec.LoraRoutes.CONV_*_GEMM issue the general convolution exactly where profiles/lora_conv_time.json has it winning beyond the
     repeat spread, at every measured shape and rank; rank 4 (Cout % 8) never goes there."""
-    from aozora_sdxl_training_amd.unet import AozoraUNet as U
+    from aozora_sdxl_training_amd.lora_exec import LoraRoutes as U
     prof = json.load(open(os.path.join(ROOT, "profiles", "lora_conv_time.json")))["kernels"]
-    rules = {"down": U._LORA_CONV_DOWN_GEMM, "dgrad": U._LORA_CONV_DGRAD_GEMM, "wgrad": U._LORA_CONV_WGRAD_GEMM}
+    rules = {"down": U.CONV_DOWN_GEMM, "dgrad": U.CONV_DGRAD_GEMM, "wgrad": U.CONV_WGRAD_GEMM}
     assert len(prof) == 8
     for label, res in prof.items():
         side, r = int(label.split("x")[0]), int(label.rsplit("r=", 1)[1])
         for product, rule in rules.items():
             m = res[product]
             assert m["general_wins_beyond_spread"] == (m["adapter"]["median_us"] - m["general"]["median_us"] > max(m["adapter"]["spread_us"], m["general"]["spread_us"]))
-            assert U._lora_conv_general(rule, 4 * side * side, r) == m["general_wins_beyond_spread"], (label, product)
+            assert U.conv_general(rule, 4 * side * side, r) == m["general_wins_beyond_spread"], (label, product)
     for rule in rules.values():
-        assert not U._lora_conv_general(rule, 1 << 20, 4) and not U._lora_conv_general(rule, 128, 64)
+        assert not U.conv_general(rule, 1 << 20, 4) and not U.conv_general(rule, 128, 64)
 
 
 # ---------------- refusals ----------------------------------------------------------------------------------------------------------------

@@ -129,7 +129,7 @@ def test_unfused_policy_and_narrowed_targets_keep_their_launches(setup):
 def test_unit_scale_takes_the_two_launch_form_where_the_general_product_is_faster(setup):
     """rank 16, alpha 16 (s = 1): at the mini configuration's 32 and 128 rows the up product is az_lora_up_bf16's and the fused kernel
     carries it (the parity test above runs that side).  With the few-row threshold lowered below them the rule of
-    AozoraUNet._lora_up_geglu sends the up product to the general product, as at the model's 4096 and 16384 rows, and az_geglu_fwd
+    lora_exec.LoraRoutes.up_geglu sends the up product to the general product, as at the model's 4096 and 16384 rows, and az_geglu_fwd
     follows: same contract, same bounds."""
     from aozora_sdxl_training_amd._lib import lib
     from aozora_sdxl_training_amd.unet_spec import LoraSpec
@@ -138,7 +138,7 @@ def test_unit_scale_takes_the_two_launch_form_where_the_general_product_is_faste
     unet = _unet(setup, spec, seed=3)
     names, _, _ = _recorded(unet, _args(pc)[1])
     assert names.count(FUSED) == BLOCKS and names.count("az_geglu_fwd") == 0
-    unet._LORA_UP_FEW_ROWS = 0
+    unet.adapters.routes.UP_FEW_ROWS = 0
     L = lib()
     L.recorder = []
     try:

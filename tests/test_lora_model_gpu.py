@@ -145,7 +145,7 @@ def test_matches_the_oracle_with_adapters(setup):
 @pytest.mark.parametrize("rank, low", [(16, False), (64, True)], ids=["rank16", "rank64-lowered-thresholds"])
 def test_unit_scale_takes_the_general_product_where_it_is_faster(setup, rank, low):
     """alpha = rank (s = 1) at latent 48x48 (1152 rows at the first attention level, 288 at the second, 154 of context): the products
-    that tools/lora_time.py found faster as az_gemm_bf16 are issued there (AozoraUNet._lora_down / _lora_up / _lora_tall), the rest as
+    that tools/lora_time.py found faster as az_gemm_bf16 are issued there (lora_exec.LoraRoutes.down / up / tall), the rest as
     az_lora_*.  rank 16: the shipped thresholds -- every tall reduction and the many-row single projections go to the general product.
     rank 64 with the row thresholds lowered to what a 48x48 latent reaches: the stacked down product and the fused accumulates too.
     Same contract, same bounds; the recorded step replays bit for bit."""
@@ -159,7 +159,7 @@ def test_unit_scale_takes_the_general_product_where_it_is_faster(setup, rank, lo
     unet.init_lora(3)
     _freeze_base(unet)
     if low:
-        unet._LORA_DOWN_GEMM_ROWS, unet._LORA_UP_FEW_ROWS = 1000, 100
+        unet.adapters.routes.DOWN_GEMM_ROWS, unet.adapters.routes.UP_FEW_ROWS = 1000, 100
     L = lib()
     L.recorder = []
     try:

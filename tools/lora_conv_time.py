@@ -8,7 +8,7 @@ tape of `inner` back-to-back launches; `spread` is max - min over the repetition
               down   u = A (*) x           [B H W][r]        vs  az_conv2d_bf16 forward, Cout = r
               dgrad  dx += A^T (*) du      [B H W][Cin]      vs  az_conv2d_bf16 data gradient over the transposed copy, accumulate
               wgrad  dA += du^T (*) x      [r][3][3][Cin]    vs  az_conv2d_bf16 weight gradient, accumulate, split_k auto
-            AozoraUNet._LORA_CONV_*_GEMM name the (rows, rank) from which the general kernel is issued: where it wins here beyond the
+            lora_exec.LoraRoutes.CONV_*_GEMM name the (rows, rank) from which the general kernel is issued: where it wins here beyond the
             spread, the adapter kernel everywhere else.
   step:     one micro-step at 1024^2, B = 4, rank 16, conv_rank 16, the base frozen: scope "unet" against scope "transformer" and
             against the full fine-tune micro-step (everything trainable, LoRA off), alternated in one process, and the launches each

@@ -8,12 +8,12 @@
               down   u = x A^T             [M][r]   = [M][K] . [r][K]^T          vs  gemm nt
               up     y += s u B^T          [M][N]  += [M][r] . [N][r]^T          vs  gemm nt, accumulate
               wgrad  dA += du^T x          [r][K]  += [M][r]^T . [M][K]          vs  gemm tn, accumulate, split_k auto
-            AozoraUNet._lora_up / _lora_tall route a product to the side that wins here (the general product where s = 1 and the rank is a
+            lora_exec.LoraRoutes.up / tall route a product to the side that wins here (the general product where s = 1 and the rank is a
             multiple of 8 allow it).
   geglu:    az_lora_up_geglu_bf16 (the up product of ff.net.0.proj with the GEGLU in its epilogue) against the two-launch form -- the up
-            product as AozoraUNet._lora_up issues it today (az_lora_up_bf16 or accumulate-az_gemm_bf16), then az_geglu_fwd -- at
+            product as lora_exec.LoraRoutes.up issues it today (az_lora_up_bf16 or accumulate-az_gemm_bf16), then az_geglu_fwd -- at
             M = 4096, H = 5120 and M = 16384, H = 2560, rank 16 and 64, s = 1 and s = 1/2.  Same procedure as `kernels`.
-            AozoraUNet._lora_up_geglu issues the side that wins here (profiles/lora_ff_time.json).
+            lora_exec.LoraRoutes.up_geglu issues the side that wins here (profiles/lora_ff_time.json).
   step:     one micro-step at 1024^2, B = 4: rank 16, alpha 16 with the base frozen -- scope "attention" (all eight projections) and
             scope "transformer" (every Linear of every Transformer2DModel) -- against the full fine-tune micro-step (everything
             trainable) of the SAME tree with LoRA off, alternated in one process; and the number of launches each records on its tape.
@@ -109,10 +109,10 @@ def kernels(reps, inner):
 
 def geglu_kernels(reps, inner):
     from aozora_sdxl_training_amd import ops
-    from aozora_sdxl_training_amd.unet import AozoraUNet
+    from aozora_sdxl_training_amd.lora_exec import LoraRoutes
     g = torch.Generator(device=DEV).manual_seed(1)
     rnd = lambda *s: (torch.randn(*s, generator=g, device=DEV) * 0.05).bfloat16()
-    rule = object.__new__(AozoraUNet)          # _lora_up reads only the class's thresholds: no model is built
+    rule = LoraRoutes()
     out = {}
     for label, M, H in GEGLU_SHAPES:
         for r in RANKS:
@@ -120,7 +120,7 @@ def geglu_kernels(reps, inner):
             proj2, o2 = proj.clone(), o.clone()
             for s in (1.0, 0.5):
                 def two(s=s):
-                    rule._lora_up(u, B, proj2, s)
+                    rule.up(u, B, proj2, s)
                     ops.geglu_fwd(proj2, o2)
                 res = ab(lambda s=s: ops.lora_up_geglu(u, B, proj, o, scale=s), two, reps, inner)
                 res = dict(fused=res["lora"], two_launch=res["gemm"], fused_wins_beyond_spread=res["lora_wins_beyond_spread"],
