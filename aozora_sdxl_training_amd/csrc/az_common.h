@@ -88,6 +88,21 @@ __device__ __forceinline__ void gelu_pair(float g, float& gelu, float& dgelu) {
 __device__ __forceinline__ float gelu_erf(float g) { float a, b; gelu_pair(g, a, b); return a; }
 __device__ __forceinline__ float dgelu_erf(float g) { float a, b; gelu_pair(g, a, b); return b; }
 
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11) in plain integer arithmetic: counter (c0 .. c3),
+// key (k0, k1) -> four words.  Shared by the stochastic-rounding parameter write (az_optim.hip) and the LoRA dropout masks (az_lora.hip).
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// 16 bits for the element in lane `l` (= e & 7) of its group: word l >> 1, low half for even l
+__device__ __forceinline__ uint32_t sr_lane_bits(const uint32_t* w, int l) { return (w[l >> 1] >> ((l & 1) << 4)) & 0xFFFFu; }
+
 // i = q * d + r for a flat element index: 32-bit division whenever the index fits (a 64-bit one is ~150 VALU instructions,
 // several times the arithmetic of the 8 elements it addresses in the element-wise kernels)
 __device__ __forceinline__ void divmod(long i, int d, long& q, int& r) {

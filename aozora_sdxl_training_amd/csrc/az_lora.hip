@@ -445,6 +445,104 @@ __global__ __launch_bounds__(256) void lora_conv_wgrad_partial_kernel(int M, int
   }
 }
 
+// ---- dropout on the adapter's inner activation (include/aozora_hip.h az_lora_dropout_bf16) --------------------------------------
+// In place on U[rows][parts r]: element (row, part p, j) is kept iff its three draws are all >= their thresholds, then scaled by inv;
+// a dropped one is SELECTED to +0.  The draws are Philox4x32-10 words of (seed; group, step, domain) in the stochastic-rounding
+// layout: element index e takes the 16 bits of lane e & 7 of group e >> 3.  The step is read from memory: a replayed launch carries
+// its scalar arguments unchanged.
+struct DropArgs {
+  uint32_t k0, k1;            // key: seed low / high word
+  int mid[3];                 // module id per part: e = (mid << 35) + ...
+  uint32_t t_net, t_rank;     // thresholds, 0 = the kind is off (nothing drawn)
+  uint32_t t_mod;
+  float inv;                  // applied iff t_net or t_rank is on
+};
+constexpr uint32_t DROP_DOM_NET = 0x10A1u, DROP_DOM_RANK = 0x10A2u, DROP_DOM_MOD = 0x10A3u;
+
+__device__ __forceinline__ void drop_group_bits(const DropArgs& a, uint32_t step, uint32_t dom, long e, uint32_t* w) {
+  const long group = e >> 3;
+  philox4x32_10((uint32_t)group, (uint32_t)((unsigned long)group >> 32), step, dom, a.k0, a.k1, w);
+}
+
+// r % 8 == 0, ldu % 8 == 0, U 16-byte aligned: one thread per 8 contiguous columns, which lie in one part, one row and one Philox
+// group of each kind (row r + j and b r + j are multiples of 8 with j).
+__global__ __launch_bounds__(256) void lora_dropout_vec_kernel(long groups, int r, int gpr, int rows_per_sample, bf16_t* __restrict__ U,
+                                                               long ldu, DropArgs a, const uint32_t* __restrict__ step_word) {
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= groups) return;
+  long row; int c8;
+  divmod(g, gpr, row, c8);
+  const int col = c8 * 8, p = col / r, j = col - p * r;
+  const uint32_t step = step_word[0];
+  const long base = (long)a.mid[p] << 35;
+  uint32_t w[4];
+  bool on = true;
+  if (a.t_mod) {
+    drop_group_bits(a, step, DROP_DOM_MOD, base, w);
+    on = sr_lane_bits(w, 0) >= a.t_mod;
+  }
+  uint32_t keep = on ? 0xFFu : 0u;               // bit l: element l of the 8 is kept
+  if (a.t_net && keep) {
+    drop_group_bits(a, step, DROP_DOM_NET, base + row * r + j, w);
+#pragma unroll
+    for (int l = 0; l < 8; ++l) if (sr_lane_bits(w, l) < a.t_net) keep &= ~(1u << l);
+  }
+  if (a.t_rank && keep) {
+    const long b = (long)((unsigned)row / (unsigned)rows_per_sample);       // row < rows < 2^31
+    drop_group_bits(a, step, DROP_DOM_RANK, base + b * r + j, w);
+#pragma unroll
+    for (int l = 0; l < 8; ++l) if (sr_lane_bits(w, l) < a.t_rank) keep &= ~(1u << l);
+  }
+  bf16x8* ptr = (bf16x8*)(U + row * ldu + col);
+  bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (keep) {
+    v = *ptr;
+    const bool scale = (a.t_net | a.t_rank) != 0;
+#pragma unroll
+    for (int l = 0; l < 8; ++l) {
+      const bf16_t x = (bf16_t)v[l];
+      const bf16_t y = scale ? f2bf(bf2f(x) * a.inv) : x;
+      v[l] = (keep >> l) & 1u ? (short)y : (short)0;
+    }
+  }
+  *ptr = v;
+}
+
+// every other shape (rank 4: 8 columns would span two parts or two rows): one thread per element, the same draws
+__global__ __launch_bounds__(256) void lora_dropout_elem_kernel(long n, int r, int width, int rows_per_sample, bf16_t* __restrict__ U, long ldu,
+                                                                DropArgs a, const uint32_t* __restrict__ step_word) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  long row; int col;
+  divmod(i, width, row, col);
+  const int p = col / r, j = col - p * r;
+  const uint32_t step = step_word[0];
+  const long base = (long)a.mid[p] << 35;
+  uint32_t w[4];
+  bool keep = true;
+  if (a.t_mod) {
+    drop_group_bits(a, step, DROP_DOM_MOD, base, w);
+    keep = sr_lane_bits(w, 0) >= a.t_mod;
+  }
+  if (a.t_net && keep) {
+    const long e = base + row * r + j;
+    drop_group_bits(a, step, DROP_DOM_NET, e, w);
+    keep = sr_lane_bits(w, (int)(e & 7)) >= a.t_net;
+  }
+  if (a.t_rank && keep) {
+    const long e = base + (long)((unsigned)row / (unsigned)rows_per_sample) * r + j;
+    drop_group_bits(a, step, DROP_DOM_RANK, e, w);
+    keep = sr_lane_bits(w, (int)(e & 7)) >= a.t_rank;
+  }
+  bf16_t* ptr = U + row * ldu + col;
+  bf16_t y = 0;
+  if (keep) {
+    y = *ptr;
+    if (a.t_net | a.t_rank) y = f2bf(bf2f(y) * a.inv);
+  }
+  *ptr = y;
+}
+
 inline bool al(const void* p, int a) { return ((uintptr_t)p & (uintptr_t)(a - 1)) == 0; }
 
 // the checks the three az_lora_conv_* entry points share: geometry, channel count, rank; -> B H W or 0
@@ -627,6 +725,38 @@ int az_lora_conv_wgrad_bf16(int B, int H, int W, int Cin, int r, float s, const 
   const long total = (long)r * nb;
   az_launch(lora_wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, r, (int)nb, 1, nsplit, s, (const float*)P, (bf16_t*)dA,
             nb, 1L, 0L, accumulate);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+
+int az_lora_dropout_bf16(int rows, int r, int parts, int rows_per_sample, void* U, long ldu, int mid0, int mid1, int mid2, int t_net,
+                         int t_rank, int t_mod, float inv, long seed, const void* step_word, void* stream) {
+  if (parts < 1 || parts > 3) return AZ_ERR_ARG(140);
+  if (r != 4 && r != 8 && r != 16 && r != 32 && r != 64) return AZ_ERR_ARG(141);
+  // row r + j stays below the module id's bit 35 (rows < 2^29 at rank 64)
+  if (rows <= 0 || rows_per_sample <= 0 || rows % rows_per_sample || (long)rows * r > (1L << 35)) return AZ_ERR_ARG(142);
+  if (ldu < (long)parts * r) return AZ_ERR_ARG(143);
+  if (t_net < 0 || t_net > 65535 || t_rank < 0 || t_rank > 65535 || t_mod < 0 || t_mod > 65535) return AZ_ERR_ARG(144);
+  if (!step_word || !al(step_word, 4) || !U || !al(U, 2)) return AZ_ERR_ARG(145);
+  const int mids[3] = {mid0, mid1, mid2};
+  for (int p = 0; p < parts; ++p)
+    if (mids[p] < 0 || mids[p] >= (1 << 27)) return AZ_ERR_ARG(146);
+  if (!(t_net | t_rank | t_mod)) return AZ_OK;      // every kind off: nothing to draw, nothing to write, no launch
+  DropArgs a;
+  a.k0 = (uint32_t)((unsigned long)seed & 0xFFFFFFFFul); a.k1 = (uint32_t)((unsigned long)seed >> 32);
+  a.mid[0] = mid0; a.mid[1] = parts > 1 ? mid1 : 0; a.mid[2] = parts > 2 ? mid2 : 0;
+  a.t_net = (uint32_t)t_net; a.t_rank = (uint32_t)t_rank; a.t_mod = (uint32_t)t_mod; a.inv = inv;
+  const int width = parts * r;
+  bf16_t* u = (bf16_t*)U;
+  const uint32_t* sw = (const uint32_t*)step_word;
+  hipStream_t st = (hipStream_t)stream;
+  if ((r & 7) == 0 && (ldu & 7) == 0 && al(U, 16)) {
+    const long groups = (long)rows * (width / 8);
+    az_launch(lora_dropout_vec_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, groups, r, width / 8, rows_per_sample, u, ldu, a, sw);
+  } else {
+    const long n = (long)rows * width;
+    az_launch(lora_dropout_elem_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, r, width, rows_per_sample, u, ldu, a, sw);
+  }
   AZ_CHECK_LAUNCH();
   return AZ_OK;
 }

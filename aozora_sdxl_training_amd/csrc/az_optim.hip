@@ -91,22 +91,9 @@ struct SrArgs {
 // scalar tail up to n (split_for)
 struct Split { long head, groups; };
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 __device__ __forceinline__ void sr_group_bits(const SrArgs& sr, long group, uint32_t* w) {
   philox4x32_10((uint32_t)group, (uint32_t)((unsigned long)group >> 32), sr.step, sr.dom, sr.k0, sr.k1, w);
 }
-// 16 bits for the element in lane `l` (= e & 7) of its group: word l >> 1, low half for even l
-__device__ __forceinline__ uint32_t sr_lane_bits(const uint32_t* w, int l) { return (w[l >> 1] >> ((l & 1) << 4)) & 0xFFFFu; }
 
 // fp32 -> bf16 bits, rounding the MAGNITUDE up with probability (low half) / 65536: r is uniform in [0, 65536).  Non-finite values and a
 // carry into the all-ones exponent (a finite value never becomes inf) keep today's behaviour / truncate.

@@ -2,7 +2,9 @@
 `LORA_PARAMS`, the adapter file in the kohya-ss layout that ComfyUI and A1111 load, the merged model, and the loader.  Host-side
 logic only; the arithmetic is az_lora_* (csrc/az_lora.hip), placed by lora_exec.py for AozoraUNet.linear / conv.  "scope" chooses the
 linears that may carry an adapter: the attention projections (the default), every Linear of every Transformer2DModel, or those and the convolutions of every
-ResnetBlock2D ("unet": conv1 / conv2 at `conv_rank` / `conv_alpha`, kohya-ss conv_dim / conv_alpha; unet_spec.LoraSpec)."""
+ResnetBlock2D ("unet": conv1 / conv2 at `conv_rank` / `conv_alpha`, kohya-ss conv_dim / conv_alpha; unet_spec.LoraSpec).
+"network_dropout", "rank_dropout" and "module_dropout" (kohya-ss's names; INTEGRATION.md "LoRA dropout") are probabilities
+in [0, 1), 0 when absent."""
 from __future__ import annotations
 
 import json
@@ -16,6 +18,7 @@ from .unet_spec import LORA_RANKS, LORA_SCOPES, LoraSpec, lora_is_conv3, lora_mo
 
 _KEYS = ("rank", "alpha", "targets", "save_merged", "scope")
 _CONV_KEYS = ("conv_rank", "conv_alpha")        # of "scope": "unet"
+_DROP_KEYS = ("network_dropout", "rank_dropout", "module_dropout")      # kohya-ss's own names; LoraSpec.dropout, .rank_dropout, .module_dropout
 DP_REFUSAL = ("LORA_PARAMS under data parallel (more than one rank): the flat gradient exchange would move the whole frozen base's "
               "gradient (5 GB at SDXL size) for a few MB of adapters; run LoRA on one GPU")
 EMA_REFUSAL = "LORA_PARAMS with \"ema_decay\": the EMA's file writer knows only the full model (EMA of adapters is a follow-up)"
@@ -23,6 +26,20 @@ EMA_REFUSAL = "LORA_PARAMS with \"ema_decay\": the EMA's file writer knows only 
 
 def _as_bool(v) -> bool:
     return v.strip().lower() in ("true", "1", "t", "y", "yes") if isinstance(v, str) else bool(v)
+
+
+def _probability(hp, key) -> float:
+    """A dropout probability of LORA_PARAMS: a number (or a string that reads as one) in [0, 1); absent = 0."""
+    v = hp.get(key, 0.0)
+    if isinstance(v, (bool, list, tuple, dict)) or v is None:
+        raise ValueError(f"LORA_PARAMS: {key} must be one number in [0, 1), got {v!r}")
+    try:
+        p = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"LORA_PARAMS: {key} cannot be read as a number: {v!r}") from None
+    if not (0.0 <= p < 1.0):          # NaN fails both
+        raise ValueError(f"LORA_PARAMS: {key} must be >= 0 and < 1, got {v!r}")
+    return p
 
 
 def options(config, world: int = 1, ema_decay=None, cfg=None) -> Tuple[Optional[LoraSpec], bool]:
@@ -33,9 +50,10 @@ def options(config, world: int = 1, ema_decay=None, cfg=None) -> Tuple[Optional[
         return None, False
     if not isinstance(hp, dict):
         raise ValueError(f"LORA_PARAMS must be a dictionary, got {type(hp).__name__}")
-    unknown = sorted(k for k in hp if k not in _KEYS + _CONV_KEYS)
+    unknown = sorted(k for k in hp if k not in _KEYS + _CONV_KEYS + _DROP_KEYS)
     if unknown:
-        raise ValueError(f"LORA_PARAMS holds unknown key(s) {unknown}: this build reads {list(_KEYS + _CONV_KEYS)}")
+        raise ValueError(f"LORA_PARAMS holds unknown key(s) {unknown}: this build reads {list(_KEYS + _CONV_KEYS + _DROP_KEYS)}")
+    drops = [_probability(hp, k) for k in _DROP_KEYS]
     rank = hp.get("rank", 16)
     if isinstance(rank, (list, tuple, dict)):
         raise ValueError(f"LORA_PARAMS: one rank for all adapters, got {rank!r} (more than one rank is a follow-up)")
@@ -83,7 +101,7 @@ def options(config, world: int = 1, ema_decay=None, cfg=None) -> Tuple[Optional[
         raise ValueError(EMA_REFUSAL)
     if scope == "unet" and conv_rank is None:
         conv_rank = rank_i              # "conv_rank" left out = "rank" (a LoraSpec of scope "unet" names it)
-    spec = LoraSpec(rank_i, alpha, str(targets), scope, conv_rank, conv_alpha)
+    spec = LoraSpec(rank_i, alpha, str(targets), scope, conv_rank, conv_alpha, *drops)
     from .unet_spec import SDXL_BASE
     lora_modules(cfg if cfg is not None else SDXL_BASE, spec)        # a target that selects nothing / something outside the scope
     return spec, _as_bool(hp.get("save_merged", False))
@@ -118,8 +136,18 @@ def file_tensors(lora_state: Dict[str, torch.Tensor], spec: LoraSpec) -> Dict[st
 def file_metadata(spec: LoraSpec) -> Dict[str, str]:
     meta = {"ss_network_module": "networks.lora", "ss_network_dim": str(spec.rank), "ss_network_alpha": f"{float(spec.alpha):g}",
             "ss_base_model_version": "sdxl_base_v1-0"}
+    args = {}
     if spec.scope == "unet":
-        meta["ss_network_args"] = json.dumps({"conv_dim": str(spec.conv3_rank), "conv_alpha": f"{spec.conv3_alpha:g}"})
+        args.update({"conv_dim": str(spec.conv3_rank), "conv_alpha": f"{spec.conv3_alpha:g}"})
+    # kohya-ss: network_dropout has a key of its own, rank_dropout / module_dropout are network arguments (strings)
+    if spec.dropout > 0:
+        meta["ss_network_dropout"] = f"{float(spec.dropout):g}"
+    if spec.rank_dropout > 0:
+        args["rank_dropout"] = f"{float(spec.rank_dropout):g}"
+    if spec.module_dropout > 0:
+        args["module_dropout"] = f"{float(spec.module_dropout):g}"
+    if args:
+        meta["ss_network_args"] = json.dumps(args)
     return meta
 
 
@@ -194,6 +222,7 @@ def load_unet(base_path, device, cfg, spec: LoraSpec, seed: int, adapters_path=N
     if (cin, cout) != (cfg.in_channels, cfg.out_channels):
         raise ValueError(f"checkpoint has in/out channels {cin}/{cout}; this build runs {cfg.in_channels}/{cfg.out_channels}")
     unet = AozoraUNet(cfg, device, lora=spec)
+    unet.set_lora_dropout_seed(seed)          # the dropout masks follow SEED (nothing recorded yet: no cost)
     unet.load_state_dict(ckpt.read_unet_state(base_path, list(unet.state_dict())))
     if adapters_path is not None:
         unet.load_lora_state_dict(read_lora_file(adapters_path, unet))

@@ -5,7 +5,7 @@ wgrad, dgrad), and the transposed-copy jobs of the adapter matrices (wt_jobs).  
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
@@ -159,14 +159,22 @@ class LoraGroup:
     GB: torch.Tensor        # ... their gradient
     Bt: torch.Tensor        # [n r][N] transposed copies, one per part
     conv3: bool = False     # the gathered products of a 3x3 convolution: the operations below need its (B, H, W)
+    mids: List[int] = field(default_factory=list)     # module id per adapted part (index of <module>.weight in the parameter table): the dropout masks' key
 
 
 class LoraAdapters:
     """The adapters of one AozoraUNet: views of its three flat buffers by slot, grouped per layer call and cached."""
 
-    def __init__(self, slots: Dict[str, tuple], pflat, gflat, wtflat, scale_of: Callable[[str], float], trainable: Callable[[str], bool]):
+    def __init__(self, slots: Dict[str, tuple], pflat, gflat, wtflat, scale_of: Callable[[str], float], trainable: Callable[[str], bool],
+                 spec=None, mid_of: Optional[Callable[[str], int]] = None):
         self.slots, self.flats, self.scale_of, self._trainable = slots, (pflat, gflat, wtflat), scale_of, trainable
         self.routes = LoraRoutes()
+        # LoRA dropout (INTEGRATION.md "LoRA dropout"): (thresholds, inv) of a spec that has one, the seed of the masks, and the device
+        # word that holds the micro-step -- armed by AozoraUNet.begin_step for a training step, None everywhere else (no masks: eval)
+        self._mid_of = mid_of if mid_of is not None else (lambda module: 0)
+        self.drop = (spec.dropout_thresholds, spec.dropout_inv) if spec is not None and spec.has_dropout else None
+        self.seed = 0
+        self.step_word = None
         self._groups: Dict[tuple, Optional[LoraGroup]] = {}
 
     def group(self, mods, conv3=False) -> Optional[LoraGroup]:
@@ -189,7 +197,8 @@ class LoraAdapters:
             A, GA, At = views(oA, a_shape, a_shape, a_shape[::-1])
             B, GB, Bt = views(oB, (n * N, r), (n * N, r), (n * r, N))
             g = LoraGroup([p for p, _ in have], n, n == len(mods), r, N, K, self.scale_of(have[0][1]),
-                          [m + sfx for _, m in have for sfx in (".lora_A.weight", ".lora_B.weight")], A, GA, At, B, GB, Bt, conv3)
+                          [m + sfx for _, m in have for sfx in (".lora_A.weight", ".lora_B.weight")], A, GA, At, B, GB, Bt, conv3,
+                          mids=[self._mid_of(m) for _, m in have])
         self._groups[key] = g
         return g
 
@@ -201,23 +210,31 @@ class LoraAdapters:
         """(index in the stack, column part of the fused output, number of parts) per launch: one launch for a whole group."""
         return [(0, 0, g.n)] if g.full else [(i, p, 1) for i, p in enumerate(g.parts)]
 
-    def fwd(self, g, x, u, y, geom=None, geglu_out=None):
-        """u = x A_cat^T (x read once; conv3: u = A (*) x), then y_p += s u_p B_p^T on the column slices of the fused output -- with
-        `geglu_out` (ff.net.0.proj) by the product that also writes GEGLU(y) there."""
+    def dropout(self, g, t, rows_per_sample):
+        """The masks of this step on t = u or du [rows][n r], in place: one launch for the group, every part a module of its own.  Issued
+        only under a spec that has dropout AND with a step word armed."""
+        if self.drop is not None and self.step_word is not None:
+            ops.lora_dropout(t, g.r, g.n, rows_per_sample, g.mids, self.drop[0], self.drop[1], self.seed, self.step_word)
+
+    def fwd(self, g, x, u, y, geom=None, geglu_out=None, rows_per_sample=None):
+        """u = x A_cat^T (x read once; conv3: u = A (*) x), the dropout masks on u, then y_p += s u_p B_p^T on the column slices of the
+        fused output -- with `geglu_out` (ff.net.0.proj) by the product that also writes GEGLU(y) there."""
         if g.conv3:
             self.routes.conv_down(g, x, geom, u)
         else:
             self.routes.down(x, g.A, u)
+        self.dropout(g, u, rows_per_sample)
         if geglu_out is not None:
             self.routes.up_geglu(u, g.B, y, geglu_out, g.s)
             return
         for i, p, n in self._launches(g):
             self.routes.up(u[:, i * g.r:(i + n) * g.r], g.B[i * g.N:(i + n) * g.N], y[:, p * g.N:(p + n) * g.N], g.s, n)
 
-    def du(self, g, dy, du):
-        """du_p = s dy_p B_p over the transposed copies of the up matrices."""
+    def du(self, g, dy, du, rows_per_sample=None):
+        """du_p = s dy_p B_p over the transposed copies of the up matrices, then the forward pass's masks on du."""
         for i, p, n in self._launches(g):
             ops.lora_down(dy[:, p * g.N:(p + n) * g.N], g.Bt[i * g.r:(i + n) * g.r], du[:, i * g.r:(i + n) * g.r], parts=n, scale=g.s)
+        self.dropout(g, du, rows_per_sample)
 
     def wgrad(self, g, x, u, dy, du, geom=None):
         """dA_cat += du^T x (conv3: dA += du^T (*) x); dB_p += s dy_p^T u_p."""

@@ -402,6 +402,25 @@ def lora_up_geglu(u, w, proj, out, *, scale=1.0):
     return out
 
 
+def lora_dropout(u, r, parts, rows_per_sample, mids, thresholds, inv, seed, step_word):
+    """In place on u [rows][parts * r] (the down product, or du): network / rank / module dropout of az_lora_dropout_bf16.  mids: the
+    module id of each part; thresholds (t_net, t_rank, t_mod), 0 = that kind off, at least one on; inv: the rescale of the kept
+    elements; step_word: a one-element int32 / uint32 DEVICE tensor that holds the micro-step when the launch runs."""
+    rows, uc, ldu = _rows(u)
+    _req(1 <= parts <= 3 and uc == parts * r and len(mids) == parts, f"lora_dropout: u {tuple(u.shape)} is not {parts} parts of rank {r} with ids {list(mids)}")
+    _req(rows_per_sample > 0 and rows % rows_per_sample == 0, f"lora_dropout: {rows} rows are no whole samples of {rows_per_sample}")
+    _req(len(thresholds) == 3 and all(int(t) == t and 0 <= t <= 65535 for t in thresholds) and any(thresholds),
+         f"lora_dropout: thresholds {tuple(thresholds)} (three in [0, 65535], at least one on)")
+    _req(isinstance(step_word, torch.Tensor) and step_word.is_cuda and step_word.device == u.device and step_word.numel() == 1
+         and step_word.dtype in (torch.int32, torch.uint32), "lora_dropout: step_word must be one int32 / uint32 on u's device")
+    m = [int(x) for x in mids] + [0] * (3 - parts)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    with _prof("lora_dropout" + (f" {rows}x{parts}x{r}" if PROFILE_SHAPES else ""), 0.0, 4.0 * rows * parts * r):
+        lib().call("az_lora_dropout_bf16", rows, r, parts, int(rows_per_sample), _ptr(u), ldu, m[0], m[1], m[2], int(thresholds[0]),
+                   int(thresholds[1]), int(thresholds[2]), float(inv), seed - (1 << 64) if seed >= (1 << 63) else seed, _ptr(step_word), _stream())
+    return u
+
+
 def lora_wgrad(small, big, out, *, parts=1, scale=1.0, accumulate=True, small_major=True):
     """out (+)= scale * small_p^T @ big_p, summed over the rows (az_lora_wgrad_bf16).  small [M][parts * ns] (du or u), big [M][parts * nb]
     (x or dy).  small_major: out [parts * ns][nb] (dA_cat = du^T x); else out [parts * nb][ns] (the stacked dB_p = s dy_p^T u_p)."""

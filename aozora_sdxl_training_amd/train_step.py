@@ -99,6 +99,10 @@ class TrainStep:
         # micro-step (micro_step(noise_aux=noise.draw_aux(...))): like the base noise they are inputs, not device RNG.
         self.noise_spec = parse_noise_mode(noise)
         self.unet, self.mode, self.ga, self.world = unet, mode, int(grad_accum), int(world_size)
+        # LoRA dropout (unet_spec.LoraSpec.has_dropout): the micro-step that keys the masks travels per micro-step
+        # (micro_step(lora_step=...)) as one more row of the coefficient table -- the integer's bits in its first word
+        self.lora_dropout = unet.lora is not None and unet.lora.has_dropout
+        self._lora_row = (5 if self.loss_spec.needs_c else 4) if self.lora_dropout else None
         self.use_graph = use_graph
         self.use_tape = unet.policy.host_tape
         self.native_tape = unet.policy.native_tape      # re-issue the tape from C (az_tape_play); False: from Python
@@ -131,7 +135,7 @@ class TrainStep:
         self.last_pred_nhwc = None
 
     # ---------------------------------------------------------------------------------------------
-    def _coefficients(self, bk: _Bucket, timesteps, jitter, time_ids, weight_scale=1.0):
+    def _coefficients(self, bk: _Bucket, timesteps, jitter, time_ids, weight_scale=1.0, lora_step=None):
         ts = torch.as_tensor(timesteps).long().cpu()
         slot = bk.runs & 1
         if bk.host_ev[slot] is not None:
@@ -149,6 +153,9 @@ class TrainStep:
             h[3] *= float(weight_scale)
         if self.loss_spec.needs_c:
             h[4] = loss_widths(self.loss_spec, self.mode, ts, jitter)
+        if self._lora_row is not None:
+            h[self._lora_row].zero_()
+            h[self._lora_row].view(torch.int32)[0] = int(lora_step) & 0x7FFFFFFF
         if h.numel() <= 256:
             return h                              # rides in the arguments of the staging launch (_stage): no H2D copy, no event
         bk.dev.copy_(h, non_blocking=True)
@@ -243,7 +250,7 @@ class TrainStep:
             if ns.needs_shape:       # (perturb alone adds nothing to the noise itself: no shaping launch)
                 ops.noise_shape(bk.noise, bk.n_o, ns.offset, bk.n_fields, bk.n_table, bk.n_levels, bk.n_part)
             ops.noise_target_ex(MODES[self.mode], bk.lat, bk.noise, bk.dev[0], bk.dev[1], bk.n_part, bk.n_xi, ns.perturb, bk.x8, bk.target)
-        u.begin_step((B, H, W, bk.ctx.shape[1], bk.parity))
+        u.begin_step((B, H, W, bk.ctx.shape[1], bk.parity), bk.lora_word)
         pred = u.forward_nhwc(bk.x8, bk.dev[2], bk.ctx, bk.pooled, bk.tids)
         if self.loss_spec.kind == "mse":
             ops.mse_loss_fwd_bwd(pred.t.view(B, H, W, C), bk.target, bk.dev[3], 1.0 / (self.ga * self.world), bk.loss,
@@ -289,7 +296,7 @@ class TrainStep:
             bk.ntape = NativeTape(bk.tape)           # built here, not at the first replay (one-time ~40 ms of host work)
 
     def micro_step(self, latents, noise, timesteps, embeds, pooled, time_ids, jitter=None, after_tail=None, defer_join=False,
-                   weight_scale=1.0, noise_aux=None):
+                   weight_scale=1.0, noise_aux=None, lora_step=None):
         """latents (B,4,h,w) bf16 ; noise (B,4,h,w) fp32 ; timesteps (B,) int ; embeds (B,L,ctx) ;
         pooled (B,P) ; time_ids (B,6) in the compute dtype (bf16 values).  Returns the device fp32
         scalar holding this micro-step's loss (train.py:2767 reads it with .item()).
@@ -299,8 +306,16 @@ class TrainStep:
         defer_join (needs double_buffer=True): do not wait for this micro-step's parameter-gradient branch; the gradient
         buffer is complete only after the next micro_step called WITHOUT defer_join (the last one of the window).
         noise_aux: the draws of TrainStep(noise=...) for this micro-step (noise.draw_aux; this rank's rows under data parallel):
-        required by a spec that draws, refused by one that does not."""
+        required by a spec that draws, refused by one that does not.
+        lora_step: the global micro-step that keys the LoRA dropout masks of this micro-step (masks are a function of the seed and of
+        it alone): required when the UNet's LoraSpec has dropout, refused when it has none."""
         u = self.unet
+        if self.lora_dropout and lora_step is None:
+            raise AozoraError("the UNet's LoraSpec has dropout: micro_step needs lora_step (the global micro-step that keys the masks)")
+        if not self.lora_dropout and lora_step is not None:
+            raise AozoraError("lora_step given, but the UNet's LoraSpec has no dropout (or the UNet has no adapters)")
+        if lora_step is not None and not (isinstance(lora_step, int) and not isinstance(lora_step, bool) and 0 <= lora_step < 2 ** 31):
+            raise AozoraError(f"lora_step must be a whole number in [0, 2^31), got {lora_step!r}")
         B, C, H, W = latents.shape
         L = embeds.shape[1]
         u.check_latent_shape(H, W)
@@ -318,7 +333,10 @@ class TrainStep:
             u._defer_join = bool(defer_join)
             u._pool_parity = parity
             if key not in self._buckets:
-                bk = _Bucket(u.device, B, C, H, W, L, u.cfg.cross_attention_dim, u.cfg.pooled_dim, 5 if self.loss_spec.needs_c else 4)
+                bk = _Bucket(u.device, B, C, H, W, L, u.cfg.cross_attention_dim, u.cfg.pooled_dim,
+                             (5 if self.loss_spec.needs_c else 4) + int(self.lora_dropout))
+                # the device word of the dropout masks' micro-step: a fixed address per bucket, written by the staging launch
+                bk.lora_word = bk.dev[self._lora_row].view(torch.int32)[:1] if self.lora_dropout else None
                 bk.tids = torch.empty(B, 6, dtype=F32, device=u.device)
                 bk.parity = parity
                 if self.noise_spec.needs_aux:
@@ -328,7 +346,7 @@ class TrainStep:
             if bk.gen != gen:                   # what this bucket recorded points into an arena that is gone
                 bk.discard_recorded()
                 bk.gen = gen
-            coef = self._coefficients(bk, timesteps, jitter, time_ids, weight_scale)
+            coef = self._coefficients(bk, timesteps, jitter, time_ids, weight_scale, lora_step)
             pairs = [(bk.lat, latents.to(BF16)), (bk.noise, noise.to(bk.noise.dtype)), (bk.ctx, embeds.to(BF16)),
                      (bk.pooled, pooled.to(BF16)), (bk.tids, time_ids.float())]
             if noise_aux is not None:            # at most three more segments: az_stage_inputs takes eight

@@ -238,14 +238,19 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     excl = getattr(config, "UNET_EXCLUDE_TARGETS", []) or []
     if isinstance(excl, str):                                                        # "a, b" -> ["a", "b"] (train.py:304-307)
         excl = [k.strip() for k in excl.split(",") if k.strip()]
+    lora_drop = lora_spec is not None and lora_spec.has_dropout
     if lora_spec is not None:        # the whole base frozen, every adapter trainable: one contiguous range of the flat buffers
         for n, p in unet.named_parameters():
             p.requires_grad = ".lora_" in n
+        if lora_drop:                # the masks are a function of (SEED, global micro-step): nothing of them goes into a training state
+            unet.set_lora_dropout_seed(config.SEED)
         if rank == 0:
             n_ad = sum(p.numel() for n, p in unet.named_parameters() if ".lora_" in n)
+            drops = (f", dropout {lora_spec.dropout:g} / rank_dropout {lora_spec.rank_dropout:g} / module_dropout {lora_spec.module_dropout:g}"
+                     if lora_drop else "")
             n_conv = sum(n.endswith(".lora_A.weight") and p.dim() == 4 for n, p in unet.named_parameters())
             convs = f" and {n_conv} adapted 3x3 convolutions at conv_rank {lora_spec.conv3_rank}, conv_alpha {lora_spec.conv3_alpha:g}" if n_conv else ""
-            print(f"INFO: LoRA is ON (rank {lora_spec.rank}, alpha {lora_spec.alpha:g}, scope {lora_spec.scope}, {len(unet.lora_state_dict()) // 2 - n_conv} adapted linears{convs}, {n_ad} "
+            print(f"INFO: LoRA is ON (rank {lora_spec.rank}, alpha {lora_spec.alpha:g}, scope {lora_spec.scope}{drops}, {len(unet.lora_state_dict()) // 2 - n_conv} adapted linears{convs}, {n_ad} "
                   f"trainable elements{', merged model saved too' if lora_merged else ''}): an option outside the reference; the base is frozen, "
                   "UNET_EXCLUDE_TARGETS is not applied, and every model file holds the adapters alone (kohya-ss layout)")
     else:
@@ -497,7 +502,7 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
                     # reached the copy, i.e. until the PREVIOUS micro-step has finished (cProfile: 115 ms per micro-step inside `.to`) -- the
                     # loop then never runs ahead of the GPU and every hiccup of the host idles it
                     loss = step.micro_step(latents, noise, timesteps, batch["embeds"], batch["pooled"], tids, jitter, after_tail=optimizer.reduce_tail if (dp and last and optimizer.overlap) else None,
-                                           weight_scale=wscale, noise_aux=noise_aux)
+                                           weight_scale=wscale, noise_aux=noise_aux, lora_step=micro_step if lora_drop else None)
                     slot = micro_step % RING
                     loss_dev[slot:slot + 1].copy_(loss, non_blocking=True)
                 else:                                            # fewer samples than ranks: this rank sits the micro-step out

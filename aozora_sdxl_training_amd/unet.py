@@ -232,7 +232,10 @@ class AozoraUNet:
         self._table = self._base_table + (lora_table(cfg, lora) if lora is not None else [])
         self._layout()
         # the adapter executor (lora_exec.py): groups, routing rules and the four per-group operations linear() / conv() call
-        self.adapters = LoraAdapters(self._slots, self.pflat, self.gflat, self.wtflat, lora.scale_of, self._trainable) if lora is not None else None
+        mids = {n[:-len(".weight")]: i for i, (n, _) in enumerate(self._base_table) if n.endswith(".weight")}
+        self.adapters = (LoraAdapters(self._slots, self.pflat, self.gflat, self.wtflat, lora.scale_of, self._trainable, lora, mids.__getitem__)
+                         if lora is not None else None)
+        self._step_B = 1              # samples of the current step (forward_nhwc): rows / B = the rows of one sample, for rank dropout
         self._pools: Dict[tuple, _Pool] = {}
         self._pool: Optional[_Pool] = None
         self._arenas: Dict[int, _Arena] = {}     # parity -> the arena its pools share (survives _pools.clear())
@@ -278,6 +281,9 @@ class AozoraUNet:
         """diffusers call signature used at train.py:2760-2761; returns an object with `.sample` (B,C,H,W) bf16."""
         if added_cond_kwargs is None or "text_embeds" not in added_cond_kwargs or "time_ids" not in added_cond_kwargs:
             raise ValueError("SDXL needs added_cond_kwargs={'text_embeds', 'time_ids'}")
+        if self.lora is not None and self.lora.has_dropout and torch.is_grad_enabled():
+            raise AozoraError("this UNet's LoraSpec has dropout: its masks are keyed by the micro-step, which only "
+                              "TrainStep.micro_step(lora_step=...) supplies; call the UNet under torch.no_grad() (eval: no masks) or train through TrainStep")
         B = sample.shape[0]
         t = torch.as_tensor(timestep, device=self.device).reshape(-1).float()
         if t.numel() == 1:
@@ -561,6 +567,17 @@ class AozoraUNet:
         """The BASE model's tensors (adapters: lora_state_dict)."""
         self.wait_tail_params()
         return {name: self._params[name].detach() for name, _ in self._base_table}
+
+    def set_lora_dropout_seed(self, seed: int):
+        """The seed of the LoRA dropout masks (config.SEED: masks are a function of (seed, micro-step) and of nothing else).  It rides
+        in the arguments of recorded launches: a change lets go of every recorded launch tape and graph."""
+        if self.adapters is None or self.adapters.seed == int(seed):
+            return
+        torch.cuda.synchronize(self.device)
+        self.adapters.seed = int(seed)
+        for ts in list(self._arena_clients):
+            for bk in ts._buckets.values():
+                bk.discard_recorded()
 
     def lora_state_dict(self):
         self.wait_tail_params()
@@ -858,9 +875,10 @@ class AozoraUNet:
 
     # ---- the adapter of a layer (lora_exec.LoraGroup `lg`): linear() and conv() place its launches through these three
     def _adapter_fwd(self, lg, x: Act, y: Act, geom=None, geglu_out: Optional[Act] = None):
-        """The adapter follows the base product: u is taken from the pool behind y.  -> (u, whether the adapter is trainable)."""
+        """The adapter follows the base product: u is taken from the pool behind y.  -> (u, whether the adapter is trainable).
+        The rows of one sample (rank dropout): rows / B -- the context length for the K / V of a cross-attention, H W for a convolution."""
         u = self._new(x.t.shape[0], lg.n * lg.r, need_grad=False)
-        self.adapters.fwd(lg, x.t, u.t, y.t, geom, geglu_out.t if geglu_out is not None else None)
+        self.adapters.fwd(lg, x.t, u.t, y.t, geom, geglu_out.t if geglu_out is not None else None, x.t.shape[0] // self._step_B)
         return u, self.adapters.trainable(lg)
 
     def _adapter_du_buf(self, lg, x: Act) -> Optional[Act]:
@@ -870,14 +888,15 @@ class AozoraUNet:
     def _adapter_bwd(self, lg, l_train, x: Act, u: Act, dy, du: Act, geom=None):
         """Behind the base layer's weight gradient, in front of its data gradient: du on the chain if the input has a gradient, and the
         adapter's weight gradients on the branch.  (The layer adds adapters.dgrad to dx itself, directly behind its own data gradient.)"""
+        rps = x.t.shape[0] // self._step_B
         if x.need_grad:
-            self.adapters.du(lg, dy, du.t)
+            self.adapters.du(lg, dy, du.t, rps)
         if l_train:
             def wgrad():
                 # without an input gradient (the text context) nothing on the chain reads du, and dy may itself be produced on the
                 # branch (the dK | dV kernel of a cross-attention): du then runs there too, in order behind its producer
                 if not x.need_grad:
-                    self.adapters.du(lg, dy, du.t)
+                    self.adapters.du(lg, dy, du.t, rps)
                 self.adapters.wgrad(lg, x.t, u.t, dy, du.t, geom)
             self._side_defer(wgrad)
 
@@ -1443,8 +1462,12 @@ class AozoraUNet:
         if H < lo or W < lo:
             raise AozoraError(f"latent shape {H}x{W} cannot run: each side must be at least {lo}")
 
-    def begin_step(self, key):
+    def begin_step(self, key, lora_step_word: Optional[torch.Tensor] = None):
+        """lora_step_word: the device word that holds this step's micro-step for the LoRA dropout masks (TrainStep arms it under a spec
+        that has dropout); None = no masks (the drop-in __call__ path never arms one)."""
         lib()._fn["az_make_current"](self._ctx)      # this thread's launches read THIS UNet's option table from here on
+        if self.adapters is not None:
+            self.adapters.step_word = lora_step_word
         arena = self._arena_of(key[-1])
         if lib().recorder is None:
             self._settle_arena(arena)
@@ -1471,6 +1494,7 @@ class AozoraUNet:
         cfg = self.cfg
         B, H, W_, _ = x8.shape
         self.check_latent_shape(H, W_)
+        self._step_B = B              # rows / B = the rows of one sample (rank dropout of an adapter: _adapter_fwd / _adapter_bwd)
         L = ctx.shape[1]
         ch = cfg.block_out_channels
         nlev = len(ch)

@@ -157,6 +157,11 @@ def lora_is_conv3(module: str) -> bool:
     return module.rsplit(".", 1)[-1] in LORA_CONVS and ".resnets." in module
 
 
+def lora_dropout_threshold(p: float) -> int:
+    """t = clamp(int(p 65536 + 0.5), 1, 65535) for p > 0, 0 for p = 0: 16 uniform bits >= t keep an element with probability 1 - t / 65536."""
+    return 0 if p <= 0.0 else min(65535, max(1, int(p * 65536.0 + 0.5)))
+
+
 @dataclass(frozen=True)
 class LoraSpec:
     """rank-r adapters: y += (alpha / rank) (x A^T) B^T.  scope: which layers may carry one -- "attention" (the default): the eight
@@ -166,15 +171,24 @@ class LoraSpec:
     convolutions; the 1x1 conv_shortcut takes rank / alpha like a Linear.  Scope "unet" carries its conv_rank explicitly (LORA_PARAMS
     may leave it out: lora.options puts rank there); conv_alpha None = alpha.  targets: comma-separated keywords
     read by the freeze keywords' rule (fnmatch(name, kw if '*' in kw else '*kw*')) against the module names of the scope; '' or
-    '*' = all."""
+    '*' = all.  dropout / rank_dropout / module_dropout: kohya-ss network, rank and module dropout of the adapters' inner activation, each
+    a probability in [0, 1) (INTEGRATION.md "LoRA dropout"); all three 0 (the default) = off, and such a spec equals one built without them."""
     rank: int = 16
     alpha: float = 16.0
     targets: str = ""
     scope: str = "attention"
     conv_rank: Optional[int] = None
     conv_alpha: Optional[float] = None
+    # LoRA dropout (INTEGRATION.md "LoRA dropout"; kohya-ss network_dropout, rank_dropout, module_dropout), each a probability in [0, 1)
+    dropout: float = 0.0
+    rank_dropout: float = 0.0
+    module_dropout: float = 0.0
 
     def __post_init__(self):
+        for key in ("dropout", "rank_dropout", "module_dropout"):
+            p = getattr(self, key)
+            if isinstance(p, bool) or not isinstance(p, (int, float)) or not (0.0 <= float(p) < 1.0):
+                raise ValueError(f"LoRA {key} must be a real number in [0, 1), got {p!r}")
         if self.rank not in LORA_RANKS:
             raise ValueError(f"LoRA rank {self.rank!r} is not one of {LORA_RANKS}")
         if not (float(self.alpha) > 0.0):
@@ -212,6 +226,20 @@ class LoraSpec:
 
     def scale_of(self, module: str) -> float:
         return self.alpha_of(module) / self.rank_of(module)
+
+    @property
+    def has_dropout(self) -> bool:
+        return float(self.dropout) > 0.0 or float(self.rank_dropout) > 0.0 or float(self.module_dropout) > 0.0
+
+    @property
+    def dropout_thresholds(self) -> Tuple[int, int, int]:
+        """(t_net, t_rank, t_mod): an element is kept iff its 16 random bits are >= t; 0 = the kind is off and draws nothing."""
+        return tuple(lora_dropout_threshold(float(p)) for p in (self.dropout, self.rank_dropout, self.module_dropout))
+
+    @property
+    def dropout_inv(self) -> float:
+        """1 / ((1 - dropout)(1 - rank_dropout)) in double; the kernel takes it rounded to fp32 (module dropout is not rescaled)."""
+        return 1.0 / ((1.0 - float(self.dropout)) * (1.0 - float(self.rank_dropout)))
 
 
 def lora_modules(cfg: UNetConfig, spec: LoraSpec) -> List[str]:

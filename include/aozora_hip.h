@@ -613,6 +613,35 @@ int az_lora_conv_dgrad_bf16(int B, int H, int W, int Cin, int r, float s, const 
 int az_lora_conv_wgrad_bf16(int B, int H, int W, int Cin, int r, float s, const void* dU, long ldu, const void* X, long ldx, void* dA,
                             int accumulate, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- LoRA dropout (kohya-ss network_dropout / rank_dropout / module_dropout; INTEGRATION.md "LoRA dropout"; tests/lora_dropout_ref.py
+ *      restates it in numpy) ----------------------------------------------------------------------------------------------------
+ * In place on the adapter's inner activation U[rows][parts r] (bf16, row stride ldu; u in the forward pass, du in the backward
+ * pass), part p of module id mid_p, sample(row) = row / rows_per_sample:
+ *     m[row][p][j] = keep_net[row][p][j] * keep_rank[sample(row)][p][j] * keep_mod[p]                  (each 0 or 1)
+ *     U[row][p r + j] = m ? bf16(float(U[row][p r + j]) * inv) : +0.0 (bits 0x0000)
+ * A dropped element is SELECTED to +0, never multiplied: a dropped inf or NaN leaves nothing behind.  inv is applied iff t_net or
+ * t_rank is nonzero (the caller passes float(1 / ((1 - p_net)(1 - p_rank))) evaluated in double; module dropout is not rescaled).
+ * Columns at and beyond parts r are never touched.
+ * The random bits: Philox4x32-10 in the layout of the stochastic-rounding write (tests/sr_ref.sr_bits16(seed, step, domain, e)):
+ * key = (seed low word, seed high word); counter = (group low word, group high word, step, domain) with group = e >> 3; element e
+ * takes the low (e even) or high (e odd) half of output word (e & 7) >> 1.  `step` is the uint32 at step_word, a DEVICE pointer (a
+ * native tape and a captured graph replay their scalar arguments unchanged, so the micro-step is read from memory; the module ids
+ * go by value for the same reason).  mid = the index of `<module>.weight` in unet_spec.param_table(cfg): a module's masks do not
+ * depend on scope, targets or which neighbours are adapted.
+ *     keep_net[row][j]   e = (mid << 35) + row r + j                  domain 0x10A1
+ *     keep_rank[b][j]    e = (mid << 35) + b r + j                    domain 0x10A2
+ *     keep_mod           e = mid << 35                                domain 0x10A3
+ * An element is kept iff its 16 bits are >= t, where t = clamp(int(p 65536 + 0.5), 1, 65535) for p > 0; a kind with p = 0 has t = 0,
+ * draws nothing and multiplies nothing.  With r % 8 == 0, ldu % 8 == 0 and U 16-byte aligned one thread covers 8 contiguous columns
+ * (one 16-byte load, one 16-byte store, one Philox evaluation per kind that is on: such a group never straddles a part or a row);
+ * every other shape (rank 4) takes a per-element kernel with the same bits.  All three t = 0 returns 0 without a launch.
+ * Argument errors, nothing launched: parts outside 1..3 (-1140); r not one of 4, 8, 16, 32, 64 (-1141); rows <= 0, rows_per_sample
+ * <= 0, rows % rows_per_sample != 0 or rows r > 2^35 (-1142); ldu < parts r (-1143); a t outside [0, 65535] (-1144); a null or
+ * misaligned step_word or U (-1145); a module id of a used part outside [0, 2^27) (-1146). */
+/* ref: not in the reference (train.py is full fine-tuning only); kohya-ss networks/lora.py LoRAModule.forward */
+int az_lora_dropout_bf16(int rows, int r, int parts, int rows_per_sample, void* U, long ldu, int mid0, int mid1, int mid2, int t_net,
+                         int t_rank, int t_mod, float inv, long seed, const void* step_word, void* stream);
+
 /* ---- native launch tape: the executor seam (SURVEY.md 8b "az_unet_step") ----------------------------------------------------
  * The step's launch sequence is static (same entry points, pointers, streams and events every step of a resolution bucket).  The
  * host executor records it once; az_tape_play re-issues it from C: entry-point calls (arguments as 64-bit words: int / long by
