@@ -465,7 +465,7 @@ class ShardedRaven:
         out = []
         for i in regions:
             self._gather_region(i)
-            self.unet._refresh_jobs(*self.regions[i])
+            self.unet.params.refresh_region(*self.regions[i])
             ev = torch.cuda.Event(); ev.record(self.comm)
             out.append((i, ev))
         return out
@@ -507,13 +507,13 @@ class ShardedRaven:
                 upd = torch.cuda.Event(); upd.record(bg)
                 with self._span("wt_refresh", bg, 4 * (self.regions[-1][1] - self.regions[0][0])):
                     for lo, hi in self.regions:        # W^T copies: read by the next BACKWARD only, so they queue behind the updates
-                        u._refresh_jobs(lo, hi)
-                u._wt_ready = torch.cuda.Event(); u._wt_ready.record(bg)
+                        u.params.refresh_region(lo, hi)
+                u.params.wt_refreshed_on(bg)
                 self._ema_regions((1, 2), bg)          # behind the region events: the forward never waits for these
             for i, ev in later:
                 u.set_region_params_event(i, ev)
             u.transposed_refreshed_externally()
-            u._grads_busy = upd                        # whoever clears the gradients (unet.zero_grad on any stream) goes behind the update
+            u.params.grads_busy_until(upd)             # whoever clears the gradients (unet.zero_grad on any stream) goes behind the update
             self._update_inflight = True
             self._write_back(upd)
             self._boundary.__exit__()
@@ -539,7 +539,7 @@ class ShardedRaven:
             u.mark_params_dirty()
             u.transposed_refreshed_externally()
             self._upd_ev = upd
-            u._grads_busy = upd                        # a gradient clear on any stream goes behind the last update
+            u.params.grads_busy_until(upd)             # a gradient clear on any stream goes behind the last update
             self._write_back(upd)
             self._boundary.__exit__()
             return self.scal[2]
@@ -594,9 +594,9 @@ class ShardedRaven:
             # no gradient
             u = self.unet
             with torch.cuda.stream(self._bg):          # (in order behind the update on that stream: no wait needed)
-                u._grads_busy = None
+                u.params.grads_busy_until(None)
                 u.zero_grad(set_to_none)
-                u._wt_ready = torch.cuda.Event(); u._wt_ready.record(self._bg)
+                u.params.wt_refreshed_on(self._bg)
             self._update_inflight = False
             return
         upd, self._upd_ev = getattr(self, "_upd_ev", None), None
@@ -609,7 +609,7 @@ class ShardedRaven:
             side.wait_event(upd)
             with torch.cuda.stream(side):
                 u.zero_grad(set_to_none)
-                u._wt_ready = torch.cuda.Event(); u._wt_ready.record(side)
+                u.params.wt_refreshed_on(side)
             return
         self.unet.zero_grad(set_to_none)
 

@@ -49,7 +49,7 @@ def read_options(params) -> Tuple[Optional[float], bool]:
 
 def logical_views(unet, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
     """{diffusers name: logical-shape view} over any flat_numel buffer in the storage order of unet.pflat: 4-D weights are stored
-    [Cout][kh][kw][Cin padded] and read (Cout, Cin, kh, kw) -- the views AozoraUNet._layout lays over pflat."""
+    [Cout][kh][kw][Cin padded] and read (Cout, Cin, kh, kw) -- the views ParamStore._layout lays over pflat."""
     out = {}
     for name, _ in unet._table:
         o, st, shape = unet._slots[name]

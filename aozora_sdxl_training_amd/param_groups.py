@@ -11,7 +11,7 @@ import fnmatch
 import math
 from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
-ALIGN = 64              # elements: a slot of the flat buffers is padded to it (unet.ALIGN); the padding belongs to its parameter's segment
+ALIGN = 64              # elements: a slot of the flat buffers is padded to it (params.ALIGN); the padding belongs to its parameter's segment
 MAX_GROUPS = 255
 _KEYS = ("match", "lr_scale", "weight_decay")
 HOST_PATH_REFUSAL = ("param_groups does not combine with {what}: that path streams pinned-host memory through the chunk pipeline, and no "

@@ -128,7 +128,7 @@ def test_ema_follows_the_parameters_bit_for_bit(grads, kind):
     # (e) copy_to: every parameter becomes bf16(ema), round to nearest even
     final = {n: t.clone() for n, t in ema.state_dict().items()}
     ema.copy_to(u)
-    assert u._wt_dirty
+    assert u.params._wt_dirty
     for n, p in u.state_dict().items():
         assert torch.equal(p.detach(), final[n].bfloat16()), n
     with pytest.raises(ValueError):                                     # a range must lie inside a tracked one (refused before any launch)

@@ -1,6 +1,6 @@
 """lora_exec.LoraRoutes and lora_exec.wt_jobs without a device: the shipped thresholds, every routing predicate on both sides of its
 edges (the table is read off the rules as they stood inside AozoraUNet), the independence of per-instance overrides, and the
-transposed-copy jobs of a hand-made slot table."""
+transposed-copy jobs of small adapter tables laid out by params.ParamStore."""
 import os
 import sys
 
@@ -11,6 +11,7 @@ sys.path.insert(0, ROOT)
 
 from aozora_sdxl_training_amd._lib import AozoraError                      # noqa: E402
 from aozora_sdxl_training_amd.lora_exec import LoraRoutes, wt_jobs        # noqa: E402
+from aozora_sdxl_training_amd.params import ParamStore                    # noqa: E402
 
 T, F = True, False
 DEFAULTS = dict(DOWN_GEMM_ROWS=8192, DOWN_GEMM_RANK=64, UP_FEW_ROWS=512, UP_FEW_RANK=32, UP_FUSED_ROWS=4096, UP_FUSED_RANK=16,
@@ -71,21 +72,14 @@ def test_instances_are_independent():
         assert getattr(b, name) == value and getattr(LoraRoutes, name) == value, name
 
 
-# ---------------- the transposed-copy jobs: slots as AozoraUNet._layout makes them, name -> (offset, storage shape, logical shape) -----------
+# ---------------- the transposed-copy jobs: slots as ParamStore._layout makes them, name -> (offset, storage shape, logical shape) -------------
 A_, B_ = ".lora_A.weight", ".lora_B.weight"
 
 
 def _slots(entries):
-    """(name, storage shape) in table order -> (table, slots), every slot rounded up to 64 elements."""
-    table, slots, off = [], {}, 0
-    for name, st in entries:
-        n = 1
-        for v in st:
-            n *= v
-        table.append((name, st))
-        slots[name] = (off, st, st)
-        off += (n + 63) // 64 * 64
-    return table, slots
+    """(name, logical shape) in table order -> (table, slots) of the real layout: a store of adapter entries only, on the CPU.  The store's
+    constructor makes the same wt_jobs call over them: a table that wt_jobs refuses is refused in here already, with the same error."""
+    return entries, ParamStore(None, entries, 0, "cpu")._slots
 
 
 def test_three_adjacent_down_matrices_are_one_job():
@@ -98,20 +92,18 @@ def test_three_adjacent_down_matrices_are_one_job():
 
 
 def test_a_fourth_adjacent_down_matrix_is_refused():
-    table, slots = _slots([(p + A_, (4, 128)) for p in ("q", "k", "v", "w")])
     with pytest.raises(AozoraError, match="at most 3 parts"):
-        wt_jobs(table, slots)
+        wt_jobs(*_slots([(p + A_, (4, 128)) for p in ("q", "k", "v", "w")]))
 
 
 def test_a_4d_down_matrix_is_a_conv_job():
     r, Cin, N = 8, 64, 128
-    table, slots = _slots([("c1" + A_, (r, 3, 3, Cin)), ("c1" + B_, (N, r)), ("sc" + A_, (4, 64)), ("sc" + B_, (N, 4))])
+    table, slots = _slots([("c1" + A_, (r, Cin, 3, 3)), ("c1" + B_, (N, r)), ("sc" + A_, (4, 64)), ("sc" + B_, (N, 4))])
     lin, conv = wt_jobs(table, slots)
     assert conv == [(0, r, Cin)]
     assert lin == [(slots["c1" + B_][0], N, r), (slots["sc" + A_][0], 4, 64), (slots["sc" + B_][0], N, 4)]
 
 
 def test_a_slot_that_is_no_multiple_of_64_elements_is_refused():
-    table, slots = _slots([("q" + A_, (4, 24)), ("q" + B_, (128, 4))])
     with pytest.raises(AozoraError, match="64-element slots"):
-        wt_jobs(table, slots)
+        wt_jobs(*_slots([("q" + A_, (4, 24)), ("q" + B_, (128, 4))]))

@@ -776,3 +776,21 @@ def test_fork_events_order_two_streams_and_equal_torch_events_bitwise(setup):
         l, g = window(fork, native, fuse)
         assert l == ref_l
         assert torch.equal(g, ref_g)
+
+
+@pytest.mark.gpu
+def test_the_parameter_store_is_the_only_holder_of_its_state(setup):
+    """AozoraUNet shows the flat buffers and the dicts of its ParamStore (params.py) as the same objects, and holds no copy of the
+    store's mutable state: the dirty flag, the version, the events, the pending set and the tables live on the store alone."""
+    from aozora_sdxl_training_amd.train_step import TrainStep
+    pc, oc, params, unet = setup
+    lat, noise, ctx, pooled, tid, ts, jit = _inputs(1, 8, 8, pc)
+    step = TrainStep(unet, mode="epsilon", grad_accum=1, use_graph=False)
+    unet.zero_grad()
+    assert math.isfinite(step.micro_step(lat.to(DEV), noise.to(DEV), ts, ctx.to(DEV), pooled.to(DEV), tid.to(DEV), jit).item())
+    step.synchronize()
+    for name in ("pflat", "gflat", "wtflat", "_slots", "_w", "_gw", "_params", "_gviews"):
+        assert getattr(unet, name) is getattr(unet.params, name), name
+    for name in ("_wt_dirty", "_wt_version", "_wt_ready", "_region_events", "_wt_region_pending", "_grads_busy", "_wt_tables"):
+        assert name not in unet.__dict__ and name in unet.params.__dict__, name
+    assert not unet.params._wt_dirty and unet.params._wt_tables
