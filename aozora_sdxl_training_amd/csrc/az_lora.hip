@@ -7,6 +7,8 @@
 // Operand maps of the MFMA: lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15], j = 0..7; the result
 // D[row = 4 (l >> 4) + i][col = l & 15], i = 0..3.  No floating-point atomics anywhere: every sum has a fixed order.
 // Behind them, the same three shapes for an adapter on a 3x3 convolution (az_lora_conv_*): the big operand gathered over the nine taps.
+// Last, the two passes that are no product of activations: the dropout masks (az_lora_dropout_bf16) and max-norm regularisation
+// (az_lora_max_norm_bf16: the Gram matrices A A^T and B^T B of every module in one launch).
 #include "az_common.h"
 #include "aozora_hip.h"
 
@@ -543,6 +545,171 @@ __global__ __launch_bounds__(256) void lora_dropout_elem_kernel(long n, int r, i
   *ptr = y;
 }
 
+// ---- max-norm regularisation (kohya-ss scale_weight_norms): || s B A ||_F of every adapted module, both matrices scaled down where it
+// exceeds the limit.  || B A ||_F^2 = sum_ij (A A^T)_ij (B^T B)_ij: two r x r Gram matrices, neither they nor the product reach memory.
+// One workgroup per module (a row of the job table), so every sum has one fixed order and the result is a pure function of the inputs:
+//   G_A = A A^T   the rows of A are k-contiguous: fragments straight from memory, the 4 waves deal the k-steps among themselves
+//   G_B = B^T B   the sum runs over the ROWS of B [out][r]: 128 rows at a time are staged in LDS (row stride r + 2: the column reads of
+//                 a fragment fall on different banks), wave w takes rows 32 w .. 32 w + 31 of the stage.  An MFMA may see the k index in
+//                 any order as long as both operands agree -- here they are the same registers.
+// Both run on v_mfma_f32_16x16x32_bf16 with the rank padded to 16 by zero fragments (ranks 4 and 8 included).  The waves' partial Gram
+// matrices are added in wave order into LDS, the r^2 products are summed by block_sum, and every thread holds the same norm and takes
+// the same decision.  The scaling pass re-reads the module (out of L2) in 16-byte groups.
+struct NormJob { const bf16_t* A; const bf16_t* B; long r, K, out, s_bits; float* mA; float* mB; };      // one row of the job table: 8 words
+constexpr int MN_STAGE_ROWS = 128;
+
+template <int NT, int KU>
+__device__ __forceinline__ void mn_gram_rows(const bf16_t* A, int r, int K, f32x4 (&acc)[NT][NT]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, kq = (lane >> 4) * 8;
+  const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int k0 = wave * 32 * KU; k0 < K; k0 += 4 * 32 * KU) {
+    bf16x8 f[KU][NT];
+#pragma unroll
+    for (int u = 0; u < KU; ++u) {
+      const int k = k0 + 32 * u + kq;             // K % 8 == 0: an 8-chunk is inside or outside as a whole
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int row = t * 16 + li;
+        f[u][t] = zero8;
+        if (k < K && row < r) f[u][t] = *(const bf16x8*)(A + (long)row * K + k);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < KU; ++u) {
+#pragma unroll
+      for (int ti = 0; ti < NT; ++ti) {
+#pragma unroll
+        for (int tj = 0; tj < NT; ++tj) acc[ti][tj] = mfma16(f[u][ti], f[u][tj], acc[ti][tj]);
+      }
+    }
+  }
+}
+
+template <int NT>
+__device__ __forceinline__ void mn_gram_cols(const bf16_t* B, int r, int lg, int out, uint32_t* stage, f32x4 (&acc)[NT][NT]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
+  const int ld = r + 2;
+  const long total = (long)out * r;
+  const bf16_t* st16 = (const bf16_t*)stage;
+  for (int o0 = 0; o0 < out; o0 += MN_STAGE_ROWS) {
+    __syncthreads();                              // the readers of the previous stage are done
+    for (int c = threadIdx.x; c < MN_STAGE_ROWS * r / 8; c += 256) {
+      const long e = (long)o0 * r + 8L * c;       // out r % 8 == 0: a 16-byte group is inside or outside as a whole
+      if (e < total) {
+        const u32x4 v = *(const u32x4*)(B + e);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const int idx = 8 * c + 2 * p;          // r is even: a pair of columns never straddles a row
+          stage[((idx >> lg) * ld + (idx & (r - 1))) >> 1] = v[p];
+        }
+      }
+    }
+    __syncthreads();
+    bf16x8 f[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int i = t * 16 + li, o = wave * 32 + g * 8;
+      const bool ok = i < r && o0 + o < out;      // out % 8 == 0: 8 rows are inside or outside as a whole
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[t][j] = ok ? (short)st16[(o + j) * ld + i] : (short)0;
+    }
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti) {
+#pragma unroll
+      for (int tj = 0; tj < NT; ++tj) acc[ti][tj] = mfma16(f[ti], f[tj], acc[ti][tj]);
+    }
+  }
+}
+
+// G[row][col] = ((wave 0 + wave 1) + wave 2) + wave 3 of the waves' partial Gram matrices
+template <int NT>
+__device__ __forceinline__ void mn_gram_store(float* G, int r, const f32x4 (&acc)[NT][NT]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
+  for (int w = 0; w < 4; ++w) {
+    if (wave == w) {
+#pragma unroll
+      for (int ti = 0; ti < NT; ++ti) {
+#pragma unroll
+        for (int tj = 0; tj < NT; ++tj) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int row = ti * 16 + g * 4 + i, col = tj * 16 + li;
+            if (row < r && col < r) G[row * r + col] = w ? G[row * r + col] + acc[ti][tj][i] : acc[ti][tj][i];
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+template <int NT, int KU>
+__device__ __forceinline__ void mn_grams(const NormJob& jb, int r, int lg, float* gA, float* gB, uint32_t* stage) {
+  f32x4 acc[NT][NT];
+#pragma unroll
+  for (int ti = 0; ti < NT; ++ti) {
+#pragma unroll
+    for (int tj = 0; tj < NT; ++tj) acc[ti][tj] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  mn_gram_rows<NT, KU>(jb.A, r, (int)jb.K, acc);
+  mn_gram_store<NT>(gA, r, acc);
+#pragma unroll
+  for (int ti = 0; ti < NT; ++ti) {
+#pragma unroll
+    for (int tj = 0; tj < NT; ++tj) acc[ti][tj] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  mn_gram_cols<NT>(jb.B, r, lg, (int)jb.out, stage, acc);
+  mn_gram_store<NT>(gB, r, acc);
+}
+
+// x <- bf16(float(x) q), or with a master copy w <- w q in fp32 and x <- bf16(w): n % 8 == 0 elements in 16-byte groups
+__device__ __forceinline__ void mn_scale(bf16_t* X, float* Wm, long n, float q) {
+  for (long c = threadIdx.x; c < n / 8; c += 256) {
+    bf16x8* px = (bf16x8*)(X + 8 * c);
+    bf16x8 v;
+    if (Wm) {
+      f32x4* pw = (f32x4*)(Wm + 8 * c);
+      const f32x4 a = pw[0] * q, b = pw[1] * q;
+      pw[0] = a; pw[1] = b;
+#pragma unroll
+      for (int l = 0; l < 4; ++l) { v[l] = (short)f2bf(a[l]); v[4 + l] = (short)f2bf(b[l]); }
+    } else {
+      v = *px;
+#pragma unroll
+      for (int l = 0; l < 8; ++l) v[l] = (short)f2bf(bf2f((bf16_t)v[l]) * q);
+    }
+    *px = v;
+  }
+}
+
+__global__ __launch_bounds__(256) void lora_max_norm_kernel(const NormJob* __restrict__ jobs, float max_norm, float* __restrict__ stats) {
+  __shared__ float gA[64 * 64], gB[64 * 64], red[16];
+  __shared__ uint32_t stage[MN_STAGE_ROWS * (64 + 2) / 2];
+  const NormJob jb = jobs[blockIdx.x];
+  const int r = (int)jb.r;
+  const int lg = r == 4 ? 2 : r == 8 ? 3 : r == 16 ? 4 : r == 32 ? 5 : r == 64 ? 6 : -1;
+  // a row the table builder should never have written touches no memory and reports NaN (uniform over the block)
+  const uintptr_t ptrs = (uintptr_t)jb.A | (uintptr_t)jb.B | (uintptr_t)jb.mA | (uintptr_t)jb.mB;
+  if (lg < 0 || jb.r != r || !jb.A || !jb.B || (ptrs & 15) || jb.K <= 0 || jb.out <= 0 || ((jb.K | jb.out) & 7) || jb.K > (1L << 24) || jb.out > (1L << 24)) {
+    if (!threadIdx.x) { stats[2 * blockIdx.x] = __uint_as_float(0x7FC00000u); stats[2 * blockIdx.x + 1] = 1.f; }
+    return;
+  }
+  if (r <= 16) mn_grams<1, 4>(jb, r, lg, gA, gB, stage);
+  else if (r == 32) mn_grams<2, 4>(jb, r, lg, gA, gB, stage);
+  else mn_grams<4, 2>(jb, r, lg, gA, gB, stage);
+  float part = 0.f;
+  for (int e = threadIdx.x; e < r * r; e += 256) part += gA[e] * gB[e];
+  const float sum = block_sum(part, red);         // the same bits in every thread: one decision per module
+  const float s = __uint_as_float((uint32_t)jb.s_bits);
+  const float norm = sqrtf(s * s * sum);
+  const bool over = norm > max_norm;              // false for a NaN norm: the module stays as it is
+  const float q = over ? sqrtf(max_norm / norm) : 1.f;
+  if (!threadIdx.x) { stats[2 * blockIdx.x] = norm; stats[2 * blockIdx.x + 1] = q; }
+  if (!over) return;
+  mn_scale((bf16_t*)jb.A, jb.mA, (long)r * jb.K, q);
+  mn_scale((bf16_t*)jb.B, jb.mB, jb.out * (long)r, q);
+}
+
 inline bool al(const void* p, int a) { return ((uintptr_t)p & (uintptr_t)(a - 1)) == 0; }
 
 // the checks the three az_lora_conv_* entry points share: geometry, channel count, rank; -> B H W or 0
@@ -757,6 +924,16 @@ int az_lora_dropout_bf16(int rows, int r, int parts, int rows_per_sample, void* 
     const long n = (long)rows * width;
     az_launch(lora_dropout_elem_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, r, width, rows_per_sample, u, ldu, a, sw);
   }
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+
+int az_lora_max_norm_bf16(const void* jobs_dev, int n_modules, float max_norm, void* stats, void* stream) {
+  if (!jobs_dev || ((uintptr_t)jobs_dev & 7)) return AZ_ERR_ARG(150);
+  if (n_modules <= 0 || n_modules > 65535) return AZ_ERR_ARG(151);
+  if (!(max_norm > 0.f) || !(max_norm <= 3.402823466e38f)) return AZ_ERR_ARG(152);      // NaN fails the first, inf the second
+  if (!stats || ((uintptr_t)stats & 7)) return AZ_ERR_ARG(153);
+  az_launch(lora_max_norm_kernel, dim3((unsigned)n_modules), dim3(256), 0, (hipStream_t)stream, (const NormJob*)jobs_dev, max_norm, (float*)stats);
   AZ_CHECK_LAUNCH();
   return AZ_OK;
 }

@@ -239,6 +239,26 @@ class ShardedRaven:
         # fp32 EMA of the owned trainable elements (ema.EmaWeights; not in the reference, None = off: no launch, allocation or event
         # differs).  Given as an EmaWeights, or as dict(decay=, warmup=) from which the shard is built in the layout of m_dev / v_dev.
         self.ema = self._make_ema(ema, force_local)
+        # LoRA max-norm (lora_norm.LoraMaxNorm; not in the reference, None = off: no launch, allocation or event differs).  Set by
+        # whoever built it with master=self.master_address: step() issues its pass behind the update of the last region -- the adapters
+        # sit behind conv_out.bias -- on the stream that updated it, ahead of that region's W^T copies, events and gathers.
+        self.lora_norm = None
+        self.lora_norm_slot = None
+
+    def master_address(self, off: int, numel: int) -> int:
+        """Address of the fp32 master copy of flat [off, off + numel), which must lie inside one owned trainable range; 0 without
+        master weights."""
+        if self.w_dev is None:
+            return 0
+        for a, b, o in self._owned():
+            if a <= off and off + numel <= b:
+                return self.w_dev.data_ptr() + 4 * (o + off - a)
+        raise ValueError(f"flat [{off}, {off + numel}) lies inside none of this optimizer's owned trainable ranges")
+
+    def _lora_norm_behind(self, i, stream):
+        """The max-norm pass behind the update of region i on `stream`, if i is the region that holds the adapters (the last one)."""
+        if self.lora_norm is not None and i == len(self.ranges) - 1:
+            self.lora_norm_slot = self.lora_norm.apply(stream)
 
     def _make_ema(self, ema, force_local):
         if ema is None:
@@ -502,6 +522,7 @@ class ShardedRaven:
                 for i in (1, 2):
                     with self._span(f"update_region{i}", bg, (20 if self.master else 14) * sum(b - a for a, b in self.ranges[i])):
                         self._update_region(i, bg)
+                        self._lora_norm_behind(i, bg)  # ahead of the region's event and of the W^T copies below
                     ev = torch.cuda.Event(); ev.record(bg)
                     later.append((i, ev))
                 upd = torch.cuda.Event(); upd.record(bg)
@@ -530,6 +551,7 @@ class ShardedRaven:
                 head = self._gather_regions((0,))[0][1]
                 for i in (1, 2):
                     self._update_region(i, self.comm)
+                    self._lora_norm_behind(i, self.comm)
                 upd = torch.cuda.Event(); upd.record(self.comm)
                 later = self._gather_regions((1, 2))
                 self._ema_regions((1, 2), self.comm)   # behind the gathers and their events, ahead of the next step's updates on this stream
@@ -545,6 +567,7 @@ class ShardedRaven:
             return self.scal[2]
         for i in range(len(self.ranges)):
             self._update_region(i, main)
+            self._lora_norm_behind(i, main)
         self._finish_step(main)
         self._boundary.__exit__()
         return self.scal[2]
@@ -806,6 +829,7 @@ class ShardedTitan(ShardedRaven):
         self._reduce_and_clip(main)
         for i in range(len(self.ranges)):
             self._update_region(i, main)
+            self._lora_norm_behind(i, main)
         self._acc_started = False
         self._finish_step(main)
         return self.scal[2]

@@ -4,10 +4,12 @@ logic only; the arithmetic is az_lora_* (csrc/az_lora.hip), placed by lora_exec.
 linears that may carry an adapter: the attention projections (the default), every Linear of every Transformer2DModel, or those and the convolutions of every
 ResnetBlock2D ("unet": conv1 / conv2 at `conv_rank` / `conv_alpha`, kohya-ss conv_dim / conv_alpha; unet_spec.LoraSpec).
 "network_dropout", "rank_dropout" and "module_dropout" (kohya-ss's names; INTEGRATION.md "LoRA dropout") are probabilities
-in [0, 1), 0 when absent."""
+in [0, 1), 0 when absent.  "scale_weight_norms" (kohya-ss's name; INTEGRATION.md "LoRA max-norm") is the limit of every module's
+|| (alpha / rank) B A ||_F, enforced after every optimizer step by lora_norm.LoraMaxNorm; absent or None = off."""
 from __future__ import annotations
 
 import json
+import math
 from pathlib import Path
 from typing import Dict, Optional, Tuple
 
@@ -19,6 +21,7 @@ from .unet_spec import LORA_RANKS, LORA_SCOPES, LoraSpec, lora_is_conv3, lora_mo
 _KEYS = ("rank", "alpha", "targets", "save_merged", "scope")
 _CONV_KEYS = ("conv_rank", "conv_alpha")        # of "scope": "unet"
 _DROP_KEYS = ("network_dropout", "rank_dropout", "module_dropout")      # kohya-ss's own names; LoraSpec.dropout, .rank_dropout, .module_dropout
+_NORM_KEY = "scale_weight_norms"               # kohya-ss's own name; LoraSpec.max_norm
 DP_REFUSAL = ("LORA_PARAMS under data parallel (more than one rank): the flat gradient exchange would move the whole frozen base's "
               "gradient (5 GB at SDXL size) for a few MB of adapters; run LoRA on one GPU")
 EMA_REFUSAL = "LORA_PARAMS with \"ema_decay\": the EMA's file writer knows only the full model (EMA of adapters is a follow-up)"
@@ -42,6 +45,22 @@ def _probability(hp, key) -> float:
     return p
 
 
+def _max_norm(hp) -> Optional[float]:
+    """scale_weight_norms of LORA_PARAMS: a number (or a string that reads as one) > 0 and finite; absent or None = off."""
+    v = hp.get(_NORM_KEY)
+    if v is None:
+        return None
+    if isinstance(v, (bool, list, tuple, dict)):
+        raise ValueError(f"LORA_PARAMS: {_NORM_KEY} must be one number > 0, got {v!r}")
+    try:
+        m = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"LORA_PARAMS: {_NORM_KEY} cannot be read as a number: {v!r}") from None
+    if not (0.0 < m < math.inf):          # NaN fails both
+        raise ValueError(f"LORA_PARAMS: {_NORM_KEY} must be > 0 and finite, got {v!r}")
+    return m
+
+
 def options(config, world: int = 1, ema_decay=None, cfg=None) -> Tuple[Optional[LoraSpec], bool]:
     """config.LORA_PARAMS -> (LoraSpec or None, save_merged).  Absent or {} = off.  Everything that cannot be read or combined is
     refused here (ValueError), before a UNet is loaded."""
@@ -50,10 +69,12 @@ def options(config, world: int = 1, ema_decay=None, cfg=None) -> Tuple[Optional[
         return None, False
     if not isinstance(hp, dict):
         raise ValueError(f"LORA_PARAMS must be a dictionary, got {type(hp).__name__}")
-    unknown = sorted(k for k in hp if k not in _KEYS + _CONV_KEYS + _DROP_KEYS)
+    known = _KEYS + _CONV_KEYS + _DROP_KEYS + (_NORM_KEY,)
+    unknown = sorted(k for k in hp if k not in known)
     if unknown:
-        raise ValueError(f"LORA_PARAMS holds unknown key(s) {unknown}: this build reads {list(_KEYS + _CONV_KEYS + _DROP_KEYS)}")
+        raise ValueError(f"LORA_PARAMS holds unknown key(s) {unknown}: this build reads {list(known)}")
     drops = [_probability(hp, k) for k in _DROP_KEYS]
+    max_norm = _max_norm(hp)
     rank = hp.get("rank", 16)
     if isinstance(rank, (list, tuple, dict)):
         raise ValueError(f"LORA_PARAMS: one rank for all adapters, got {rank!r} (more than one rank is a follow-up)")
@@ -101,7 +122,7 @@ def options(config, world: int = 1, ema_decay=None, cfg=None) -> Tuple[Optional[
         raise ValueError(EMA_REFUSAL)
     if scope == "unet" and conv_rank is None:
         conv_rank = rank_i              # "conv_rank" left out = "rank" (a LoraSpec of scope "unet" names it)
-    spec = LoraSpec(rank_i, alpha, str(targets), scope, conv_rank, conv_alpha, *drops)
+    spec = LoraSpec(rank_i, alpha, str(targets), scope, conv_rank, conv_alpha, *drops, max_norm)
     from .unet_spec import SDXL_BASE
     lora_modules(cfg if cfg is not None else SDXL_BASE, spec)        # a target that selects nothing / something outside the scope
     return spec, _as_bool(hp.get("save_merged", False))
@@ -146,6 +167,8 @@ def file_metadata(spec: LoraSpec) -> Dict[str, str]:
         args["rank_dropout"] = f"{float(spec.rank_dropout):g}"
     if spec.module_dropout > 0:
         args["module_dropout"] = f"{float(spec.module_dropout):g}"
+    if spec.max_norm is not None:      # kohya-ss: a key of its own
+        meta["ss_scale_weight_norms"] = str(float(spec.max_norm))
     if args:
         meta["ss_network_args"] = json.dumps(args)
     return meta

@@ -421,6 +421,22 @@ def lora_dropout(u, r, parts, rows_per_sample, mids, thresholds, inv, seed, step
     return u
 
 
+def lora_max_norm(table, max_norm, stats, stream=None):
+    """Max-norm regularisation of every adapted module in ONE launch (az_lora_max_norm_bf16): table is the int64 DEVICE job table
+    [n][8] (lora_norm.job_rows: address of A, of B, r, K, out, fp32 bits of s, address of the fp32 master of A or 0, of B or 0), stats
+    the fp32 device array [n][2] that receives (norm before scaling, q) per module, on `stream` (default: the current one)."""
+    import math
+    _req(isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 8
+         and table.is_contiguous() and 1 <= table.shape[0] <= 65535, "lora_max_norm: table must be a contiguous cuda int64 [n][8], 1 <= n <= 65535")
+    _req(isinstance(stats, torch.Tensor) and stats.is_cuda and stats.device == table.device and stats.dtype == F32 and stats.is_contiguous()
+         and tuple(stats.shape) == (table.shape[0], 2), "lora_max_norm: stats must be a contiguous fp32 [n][2] on the table's device")
+    _req(not isinstance(max_norm, bool) and isinstance(max_norm, (int, float)) and math.isfinite(max_norm) and max_norm > 0
+         and float(max_norm) <= 3.4028234663852886e38, f"lora_max_norm: max_norm must be a positive finite number, got {max_norm!r}")
+    st = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    lib().call("az_lora_max_norm_bf16", _ptr(table), int(table.shape[0]), float(max_norm), _ptr(stats), st)
+    return stats
+
+
 def lora_wgrad(small, big, out, *, parts=1, scale=1.0, accumulate=True, small_major=True):
     """out (+)= scale * small_p^T @ big_p, summed over the rows (az_lora_wgrad_bf16).  small [M][parts * ns] (du or u), big [M][parts * nb]
     (x or dy).  small_major: out [parts * ns][nb] (dA_cat = du^T x); else out [parts * nb][ns] (the stacked dB_p = s dy_p^T u_p)."""

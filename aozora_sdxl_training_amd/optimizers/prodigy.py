@@ -154,6 +154,15 @@ class Prodigy(Optimizer):
         self._fill(("w",))
         torch.cuda.synchronize(self.param_device)
 
+    def master_address(self, off: int, numel: int) -> int:
+        """Address of the master copy w of flat [off, off + numel) of the owner's buffers, which must lie inside one range (for
+        lora_norm.LoraMaxNorm: it scales w and leaves the starting point p0 and every other state alone)."""
+        self._init_state()
+        for r, o in zip(self.ranges, self.range_off):
+            if r[0] == "flat" and r[1] <= off and off + numel <= r[2]:
+                return self.w_dev.data_ptr() + 4 * (o + off - r[1])
+        raise ValueError(f"flat [{off}, {off + numel}) lies inside none of this optimizer's ranges")
+
     def zero_grad(self, set_to_none: bool = True):
         """As PagedAdamW8bit.zero_grad: AozoraUNet gradients accumulate in the owner's flat buffer, so the buffer itself is cleared."""
         if self.owner is not None:

@@ -331,6 +331,20 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     if rank == 0 and ema is not None:
         print(f"INFO: EMA of the trainable weights is ON (decay {ema_decay}, warm-up {'on' if ema_warmup else 'off'}, {ema.nbytes} bytes of fp32 on this "
               "rank): an option outside the reference")
+    # LORA_PARAMS "scale_weight_norms" (lora_norm.py; kohya-ss's max-norm regularisation, absent = off: no launch, no buffer): one launch
+    # behind every optimizer step's update of the adapters.  The flat optimizers issue it inside step(), on the stream that updated the
+    # adapters' region and ahead of its W^T copies; a module optimizer's step() is followed by apply() + mark_params_dirty() in the loop.
+    # With an fp32 master (Raven / Titan "master_weights", Prodigy's w always) the master is scaled and the parameter is bf16(master).
+    lora_norm = None
+    if lora_spec is not None and lora_spec.max_norm is not None:
+        from .lora_norm import LoraMaxNorm
+        lora_norm = LoraMaxNorm(unet, lora_spec.max_norm, master=optimizer.master_address if (prodigy or (flat_opt and master)) else None)
+        if flat_opt:
+            optimizer.lora_norm = lora_norm
+        if rank == 0:
+            print(f"INFO: LoRA max-norm is ON (scale_weight_norms {lora_spec.max_norm:g}, {lora_norm.n} modules in one launch per optimizer step"
+                  f"{', fp32 masters scaled with them' if lora_norm.has_master else ''}): an option outside the reference; written from kohya-ss's "
+                  "rule as understood, unpinned against the package")
     lr_scheduler = CustomCurveLRScheduler(optimizer, config.LR_CUSTOM_CURVE, config.MAX_TRAIN_STEPS)
     if getattr(config, "RESUME_TRAINING", False):
         if dp:       # every rank resumes its own shard (written next to rank 0's training-state file)
@@ -380,6 +394,8 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
         hist["saved_ema"] = []
     if prodigy:
         hist["prodigy_d"] = []
+    if lora_norm is not None:
+        hist.update(lora_keys_scaled=[], lora_avg_key_norm=[], lora_max_key_norm=[])
     # emergency-save flag: the GUI writes PROJECT_ROOT/force_save.flag and runs the trainer with cwd = PROJECT_ROOT
     # (gui.py:5947, 5983; train.py:2550 looks next to itself) -> default = the process' working directory
     flag = Path(getattr(config, "FORCE_SAVE_FLAG", None) or Path.cwd() / "force_save.flag")
@@ -423,6 +439,11 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
         raw = c["raw"] if c["raw"] is not None else float(norm_host[rec["slot"]])
         hist["grad_norms"].append(raw)
         hist["lrs"].append(c["lr"])
+        if c.get("lora_norm_slot") is not None:      # the pass's statistics landed behind an event of their own: no queue is drained for them
+            n_scaled, avg_norm, max_key = lora_norm.summary(c["lora_norm_slot"])
+            hist["lora_keys_scaled"].append(n_scaled)
+            hist["lora_avg_key_norm"].append(avg_norm)
+            hist["lora_max_key_norm"].append(max_key)
         diag = dict(optim_step=c["optim_step"], avg_loss=sum(window) / len(window) if window else 0.0, current_lr=c["lr"],
                     raw_grad_norm=raw, clipped_grad_norm=min(raw, clip) if clip > 0 else raw, update_delta=1.0 if raw > 0 else 0.0,
                     optim_step_time=c["optim_step_time"], avg_optim_step_time=c["avg_optim_step_time"])
@@ -547,6 +568,13 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
                         optimizer.step()
                     if ema is not None and not flat_opt:
                         ema.update()                              # same stream, right behind the step
+                    norm_slot = None
+                    if lora_norm is not None:
+                        if flat_opt:
+                            norm_slot = optimizer.lora_norm_slot  # issued inside step(), behind the update of the adapters' region
+                        else:
+                            norm_slot = lora_norm.apply()         # same stream, right behind the step; the W^T copies follow the scaled values
+                            unet.mark_params_dirty()
                     optimizer.zero_grad(set_to_none=True)
                     optimizer_step += 1
                     if prodigy:                     # (this branch has already blocked on the norm's .item())
@@ -559,7 +587,7 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
                     optim_times.append(now - t_last_opt)
                     t_last_opt = now
                     lr_now = optimizer.param_groups[-1]["lr"]
-                    cur["closing"] = dict(raw=raw, lr=lr_now, optim_step=optimizer_step, optim_step_time=optim_times[-1],
+                    cur["closing"] = dict(raw=raw, lr=lr_now, optim_step=optimizer_step, optim_step_time=optim_times[-1], lora_norm_slot=norm_slot,
                                           avg_optim_step_time=sum(optim_times) / len(optim_times))
                     every = int(getattr(config, "SAVE_EVERY_N_STEPS", 0) or 0)
                     # rank 0 alone consumes the flag file and tells the others: every rank must take the same branch, because
@@ -572,7 +600,9 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
                     if (every > 0 and optimizer_step % every == 0) or forced:            # train.py:2805-2815
                         reason = "Emergency checkpoint requested" if forced and not (every > 0 and optimizer_step % every == 0) else "Saving checkpoint"
                         flush()                                  # the progress lines of this window come before the checkpoint's (log order of the reference)
-                        reporter.log_message(f"\n--- {reason} at optimizer step {optimizer_step} ---" + (f" (prodigy d = {optimizer.d_value():.6e})" if prodigy else ""))
+                        reporter.log_message(f"\n--- {reason} at optimizer step {optimizer_step} ---" + (f" (prodigy d = {optimizer.d_value():.6e})" if prodigy else "")
+                                             + (f" (lora max-norm: {hist['lora_keys_scaled'][-1]} keys scaled, avg key norm {hist['lora_avg_key_norm'][-1]:.6g}, "
+                                                f"max key norm {hist['lora_max_key_norm'][-1]:.6g})" if lora_norm is not None else ""))
                         mname, sname = ckpt.checkpoint_names(stem, optimizer_step)
                         if hasattr(optimizer, "synchronize_params"):
                             optimizer.synchronize_params()      # updates / all-gathers still running under the next forward's slots must have landed

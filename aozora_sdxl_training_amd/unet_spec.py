@@ -172,7 +172,8 @@ class LoraSpec:
     may leave it out: lora.options puts rank there); conv_alpha None = alpha.  targets: comma-separated keywords
     read by the freeze keywords' rule (fnmatch(name, kw if '*' in kw else '*kw*')) against the module names of the scope; '' or
     '*' = all.  dropout / rank_dropout / module_dropout: kohya-ss network, rank and module dropout of the adapters' inner activation, each
-    a probability in [0, 1) (INTEGRATION.md "LoRA dropout"); all three 0 (the default) = off, and such a spec equals one built without them."""
+    a probability in [0, 1) (INTEGRATION.md "LoRA dropout"); all three 0 (the default) = off, and such a spec equals one built without them.
+    max_norm: kohya-ss scale_weight_norms, the limit of every module's || scale B A ||_F (INTEGRATION.md "LoRA max-norm"); None = off."""
     rank: int = 16
     alpha: float = 16.0
     targets: str = ""
@@ -183,8 +184,15 @@ class LoraSpec:
     dropout: float = 0.0
     rank_dropout: float = 0.0
     module_dropout: float = 0.0
+    # LoRA max-norm (INTEGRATION.md "LoRA max-norm"; kohya-ss scale_weight_norms): the limit of || (alpha / rank) B A ||_F per module,
+    # enforced after every optimizer step; None (the default) = off, and such a spec equals one built without it
+    max_norm: Optional[float] = None
 
     def __post_init__(self):
+        if self.max_norm is not None:
+            m = self.max_norm
+            if isinstance(m, bool) or not isinstance(m, (int, float)) or not (0.0 < float(m) < float("inf")):      # NaN fails both
+                raise ValueError(f"LoRA max_norm must be a positive finite real number or None, got {m!r}")
         for key in ("dropout", "rank_dropout", "module_dropout"):
             p = getattr(self, key)
             if isinstance(p, bool) or not isinstance(p, (int, float)) or not (0.0 <= float(p) < 1.0):

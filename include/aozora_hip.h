@@ -642,6 +642,27 @@ int az_lora_conv_wgrad_bf16(int B, int H, int W, int Cin, int r, float s, const 
 int az_lora_dropout_bf16(int rows, int r, int parts, int rows_per_sample, void* U, long ldu, int mid0, int mid1, int mid2, int t_net,
                          int t_rank, int t_mod, float inv, long seed, const void* step_word, void* stream);
 
+/* ---- LoRA max-norm regularisation (kohya-ss scale_weight_norms; INTEGRATION.md "LoRA max-norm"; tests/lora_maxnorm_ref.py restates
+ *      it in numpy) -----------------------------------------------------------------------------------------------------------------
+ * After an optimizer step, for every adapted module with A[r][K] ("down", dense; a 3x3 convolution's [r][3][3][Cin] is K = 9 Cin:
+ * the norm does not depend on the order of K), B[out][r] ("up", dense) and s = alpha / rank:
+ *     G_A = A A^T,  G_B = B^T B            bf16 operands, fp32 accumulation, the summation order is the kernel's own (but fixed)
+ *     n2 = s * s * sum_ij G_A[i][j] G_B[i][j]   ( = || s B A ||_F^2 without the product)        norm = sqrtf(n2)
+ *     norm > max_norm:  q = sqrtf(max_norm / norm), and every element of A and of B
+ *                           x <- bf16(float(x) q)                                    without a master copy
+ *                           w <- w q in fp32, x <- bf16(w)                           with one (the norm is still taken from the bf16 values)
+ *     otherwise q = 1 and NOTHING of the module is written -- a NaN norm compares false; B = 0 gives norm 0, q = 1 and no NaN.
+ * stats[m] = (norm before scaling, q), fp32.  ONE launch serves every module: jobs_dev is a DEVICE table of n_modules rows of eight
+ * 64-bit words (address of A, address of B, r, K, out, the fp32 bits of s in the low half, address of the fp32 master copy of A or 0,
+ * the same for B), built once by the caller.  r is one of 4, 8, 16, 32, 64; K and out positive multiples of 8 up to 2^24; every
+ * address 16-byte aligned.  A row that breaks one of these is skipped by its workgroup -- no byte of it is read or written -- and
+ * reports (NaN, 1).  One workgroup per module, no floating-point atomics: the result is a pure function of the inputs.  Elements
+ * outside the r K and out r of a module (the padding between slots) are never touched.
+ * Argument errors, nothing launched: jobs_dev null or not 8-byte aligned (-1150); n_modules outside [1, 65535] (-1151); max_norm not
+ * a positive finite number (-1152); stats null or not 8-byte aligned (-1153). */
+/* ref: not in the reference (train.py is full fine-tuning only); kohya-ss networks/lora.py apply_max_norm_regularization */
+int az_lora_max_norm_bf16(const void* jobs_dev, int n_modules, float max_norm, void* stats, void* stream);
+
 /* ---- native launch tape: the executor seam (SURVEY.md 8b "az_unet_step") ----------------------------------------------------
  * The step's launch sequence is static (same entry points, pointers, streams and events every step of a resolution bucket).  The
  * host executor records it once; az_tape_play re-issues it from C: entry-point calls (arguments as 64-bit words: int / long by
