@@ -8,7 +8,8 @@
 // D[row = 4 (l >> 4) + i][col = l & 15], i = 0..3.  No floating-point atomics anywhere: every sum has a fixed order.
 // Behind them, the same three shapes for an adapter on a 3x3 convolution (az_lora_conv_*): the big operand gathered over the nine taps.
 // Last, the two passes that are no product of activations: the dropout masks (az_lora_dropout_bf16) and max-norm regularisation
-// (az_lora_max_norm_bf16: the Gram matrices A A^T and B^T B of every module in one launch).
+// (az_lora_max_norm_bf16: the Gram matrices A A^T and B^T B of every module in one launch).  Behind those, DoRA (az_dora_*): the row
+// norms of W + s B A of every module in one launch, the per-column gain of the forward and its backward.
 #include "az_common.h"
 #include "aozora_hip.h"
 
@@ -710,6 +711,172 @@ __global__ __launch_bounds__(256) void lora_max_norm_kernel(const NormJob* __res
   mn_scale((bf16_t*)jb.B, jb.mB, jb.out * (long)r, q);
 }
 
+// ==== DoRA (weight-decomposed LoRA; include/aozora_hip.h az_dora_*) ===================================================================
+// ---- norm: n2[o] = sum_k (float(W[o][k]) + s sum_j B[o][j] A[j][k])^2, inv = 1 / sqrt(n2), g = float(m) inv, for every adapted module in
+// one launch.  A workgroup owns 64 output rows of one module (16 per wave) and walks K in chunks of 64 columns.  The B A tile of a
+// chunk is formed on the MFMA with the contraction over the rank (padded to 32 per k-step by zero fragments): the wave's B rows are
+// loaded once (j contiguous), the chunk of A [r][64] is j-strided in memory and goes through LDS transposed, At[column][j] (row stride
+// 72 elements: 16-byte aligned fragment reads), shared by the four waves; one buffer, two barriers per chunk.  A lane owns row o0 + li
+// and the 4 consecutive columns 16 t + 4 (lane >> 4) + i of each 16-column tile: it adds W (one 8-byte load per tile, the four of a
+// chunk issued together: a row's 128 bytes), squares and accumulates in ascending column order; the four lanes of a row are added in
+// lane order.  One fixed order, no atomics.
+struct DoraJob { const bf16_t* W; const bf16_t* A; const bf16_t* B; bf16_t* m; float* g; float* inv; long r, K, N, s_bits, tile_start, pad; };   // 12 words
+constexpr int DN_ROWS = 64, DN_KC = 64, DN_LD = 72;
+
+template <int KS>
+__device__ __forceinline__ float dora_row_sumsq(const DoraJob& jb, int r, int lg, long o0, float s, bf16_t* At) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g4 = lane >> 4, kq = g4 * 8;
+  const int K = (int)jb.K;
+  const long o = o0 + wave * 16 + li;
+  const bool ook = o < jb.N;
+  bf16x8 bfr[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) bfr[ks] = load_small8(jb.B + (ook ? o : 0) * r, ks * 32 + kq, r, ook);
+  const bf16_t* wrow = jb.W + (ook ? o : 0) * K;
+  for (int e = tid; e < DN_KC * DN_LD / 8; e += 256) ((bf16x8*)At)[e] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};      // the rank's padding stays zero
+  float sq = 0.f;
+  for (int k0 = 0; k0 < K; k0 += DN_KC) {
+    __syncthreads();                              // the previous chunk's fragments have been read (first pass: the zeros are written)
+    for (int c = tid; c < r * 8; c += 256) {      // j fastest: the transposed 2-byte writes of a wave fall on consecutive addresses
+      const int j = c & (r - 1), kk = (c >> lg) * 8;
+      bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (k0 + kk < K) v = *(const bf16x8*)(jb.A + (long)j * K + k0 + kk);       // K % 8 == 0: an 8-chunk is inside or outside as a whole
+#pragma unroll
+      for (int e = 0; e < 8; ++e) At[(kk + e) * DN_LD + j] = (bf16_t)v[e];
+    }
+    __syncthreads();
+    bf16x4 w[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int k4 = k0 + 16 * t + 4 * g4;
+      w[t] = bf16x4{0, 0, 0, 0};
+      if (ook && k4 < K) w[t] = *(const bf16x4*)(wrow + k4);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) acc = mfma16(*(const bf16x8*)(At + (16 * t + li) * DN_LD + ks * 32 + kq), bfr[ks], acc);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float val = __fmaf_rn(s, acc[i], bf2f((bf16_t)w[t][i]));
+        sq = __fmaf_rn(val, val, sq);
+      }
+    }
+  }
+  const float p0 = __shfl(sq, li, 64), p1 = __shfl(sq, li + 16, 64), p2 = __shfl(sq, li + 32, 64), p3 = __shfl(sq, li + 48, 64);
+  return ((p0 + p1) + p2) + p3;
+}
+
+__global__ __launch_bounds__(256) void dora_norm_kernel(const DoraJob* __restrict__ jobs, int njobs, int init) {
+  __shared__ __attribute__((aligned(16))) bf16_t At[DN_KC * DN_LD];
+  const long tg = blockIdx.x;
+  int lo = 0, hi = njobs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].tile_start <= tg) lo = mid; else hi = mid - 1;
+  }
+  const DoraJob jb = jobs[lo];
+  const long tile = tg - jb.tile_start, o0 = tile * DN_ROWS;
+  const int r = (int)jb.r;
+  const int lg = r == 4 ? 2 : r == 8 ? 3 : r == 16 ? 4 : r == 32 ? 5 : r == 64 ? 6 : -1;
+  const bool out_ok = jb.g && jb.inv && !(((uintptr_t)jb.g | (uintptr_t)jb.inv) & 3) && jb.N > 0 && jb.N <= (1L << 24) && tile >= 0;
+  // a row the table builder should never have written (uniform over the block): nothing of W, A, B, m is touched, and where the
+  // addresses of its gains and its N can be trusted they report NaN
+  const uintptr_t ptrs = (uintptr_t)jb.W | (uintptr_t)jb.A | (uintptr_t)jb.B;
+  if (lg < 0 || jb.r != r || !jb.W || !jb.A || !jb.B || !jb.m || (ptrs & 15) || ((uintptr_t)jb.m & 1) || !out_ok || jb.K <= 0 || ((jb.K | jb.N) & 7) ||
+      jb.K > (1L << 24)) {
+    if (out_ok) {
+      const long o = o0 + threadIdx.x;
+      if (threadIdx.x < DN_ROWS && o < jb.N) { jb.g[o] = __uint_as_float(0x7FC00000u); jb.inv[o] = __uint_as_float(0x7FC00000u); }
+    }
+    return;
+  }
+  if (o0 >= jb.N) return;
+  const float s = __uint_as_float((uint32_t)jb.s_bits);
+  const float n2 = r <= 32 ? dora_row_sumsq<1>(jb, r, lg, o0, s, At) : dora_row_sumsq<2>(jb, r, lg, o0, s, At);
+  const int lane = threadIdx.x & 63;
+  const long o = o0 + (threadIdx.x >> 6) * 16 + lane;
+  if (lane < 16 && o < jb.N) {
+    const float root = sqrtf(n2), inv = 1.f / root;
+    bf16_t mm;
+    if (init) { mm = f2bf(root); jb.m[o] = mm; } else mm = jb.m[o];
+    jb.g[o] = bf2f(mm) * inv;
+    jb.inv[o] = inv;
+  }
+}
+
+// ---- scale: Y[m][o] = bf16(fmaf(g[o], float(V[m][o]), bias[o] or 0) + (float(R[m][o]) or 0)): one thread per 8 columns ----------------
+__global__ __launch_bounds__(256) void dora_scale_kernel(long groups, int gpr, const bf16_t* __restrict__ V, long ldv, const float* __restrict__ g,
+                                                         const bf16_t* __restrict__ bias, const bf16_t* __restrict__ R, long ldr, bf16_t* __restrict__ Y, long ldy) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= groups) return;
+  long row; int c8;
+  divmod(i, gpr, row, c8);
+  const int col = c8 * 8;
+  const bf16x8 v = *(const bf16x8*)(V + row * ldv + col);
+  const f32x4 g0 = *(const f32x4*)(g + col), g1 = *(const f32x4*)(g + col + 4);
+  bf16x8 b = {0, 0, 0, 0, 0, 0, 0, 0}, rr = {0, 0, 0, 0, 0, 0, 0, 0}, y;
+  if (bias) b = *(const bf16x8*)(bias + col);
+  if (R) rr = *(const bf16x8*)(R + row * ldr + col);
+#pragma unroll
+  for (int l = 0; l < 8; ++l) {
+    float t = __fmaf_rn(l < 4 ? g0[l & 3] : g1[l & 3], bf2f((bf16_t)v[l]), bias ? bf2f((bf16_t)b[l]) : 0.f);
+    if (R) t = t + bf2f((bf16_t)rr[l]);
+    y[l] = (short)f2bf(t);
+  }
+  *(bf16x8*)(Y + row * ldy + col) = y;
+}
+
+// ---- backward: dV[m][o] = bf16(g[o] float(dY[m][o])) and, with P, the partial column sums P[split][o] = sum over the split's rows of
+// float(dY) float(V) (a product of two bf16 is exact in fp32).  A block owns 256 columns (a thread 8 of them) and the rows
+// [split rps, min(M, (split + 1) rps)); its 8 row lanes take every 8th row in ascending order and are added in lane order.
+__global__ __launch_bounds__(256) void dora_bwd_kernel(int M, int N, int rps, const bf16_t* __restrict__ dY, long lddy, const bf16_t* __restrict__ V, long ldv,
+                                                       const float* __restrict__ g, bf16_t* dV, long lddv, float* __restrict__ P) {
+  __shared__ float red[8][256];
+  const int tid = threadIdx.x, cg = tid & 31, rs = tid >> 5;
+  const int col = blockIdx.x * 256 + cg * 8, split = blockIdx.y;
+  const long mbeg = (long)split * rps, mend = min((long)M, mbeg + rps);
+  const bool cok = col < N;                       // N % 8 == 0: an 8-group is inside or outside as a whole
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, gg[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (cok) {
+    const f32x4 g0 = *(const f32x4*)(g + col), g1 = *(const f32x4*)(g + col + 4);
+#pragma unroll
+    for (int l = 0; l < 4; ++l) { gg[l] = g0[l]; gg[4 + l] = g1[l]; }
+    for (long m = mbeg + rs; m < mend; m += 8) {
+      const bf16x8 dy = *(const bf16x8*)(dY + m * lddy + col);
+      bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0}, dv;
+      if (P) v = *(const bf16x8*)(V + m * ldv + col);
+#pragma unroll
+      for (int l = 0; l < 8; ++l) {
+        const float d = bf2f((bf16_t)dy[l]);
+        dv[l] = (short)f2bf(gg[l] * d);
+        acc[l] = __fmaf_rn(d, bf2f((bf16_t)v[l]), acc[l]);
+      }
+      *(bf16x8*)(dV + m * lddv + col) = dv;
+    }
+  }
+  if (!P) return;                                 // uniform over the grid
+#pragma unroll
+  for (int l = 0; l < 8; ++l) red[rs][cg * 8 + l] = acc[l];
+  __syncthreads();
+  const int c = blockIdx.x * 256 + tid;
+  if (c >= N) return;
+  float sum = red[0][tid];
+#pragma unroll
+  for (int k = 1; k < 8; ++k) sum += red[k][tid];
+  P[(long)split * N + c] = sum;
+}
+
+// dm[o] = bf16(fmaf(inv[o], sum_split P[split][o], float(dm[o]))), splits ascending
+__global__ __launch_bounds__(256) void dora_bwd_finish_kernel(int N, int nsplit, const float* __restrict__ P, const float* __restrict__ inv, bf16_t* dm) {
+  const int o = blockIdx.x * 256 + threadIdx.x;
+  if (o >= N) return;
+  float sum = 0.f;
+  for (int k = 0; k < nsplit; ++k) sum += P[(long)k * N + o];
+  dm[o] = f2bf(__fmaf_rn(inv[o], sum, bf2f(dm[o])));
+}
+
 inline bool al(const void* p, int a) { return ((uintptr_t)p & (uintptr_t)(a - 1)) == 0; }
 
 // the checks the three az_lora_conv_* entry points share: geometry, channel count, rank; -> B H W or 0
@@ -935,6 +1102,60 @@ int az_lora_max_norm_bf16(const void* jobs_dev, int n_modules, float max_norm, v
   if (!stats || ((uintptr_t)stats & 7)) return AZ_ERR_ARG(153);
   az_launch(lora_max_norm_kernel, dim3((unsigned)n_modules), dim3(256), 0, (hipStream_t)stream, (const NormJob*)jobs_dev, max_norm, (float*)stats);
   AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+
+int az_dora_norm_bf16(const void* jobs_dev, int n_modules, long tiles, int init, void* stream) {
+  if (!jobs_dev || ((uintptr_t)jobs_dev & 7)) return AZ_ERR_ARG(160);
+  if (n_modules <= 0 || n_modules > 65535) return AZ_ERR_ARG(161);
+  if (tiles <= 0 || tiles > 0x7FFFFFF0L) return AZ_ERR_ARG(162);
+  if (init != 0 && init != 1) return AZ_ERR_ARG(163);
+  az_launch(dora_norm_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, (const DoraJob*)jobs_dev, n_modules, init);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+
+int az_dora_scale_bf16(int M, int N, const void* V, long ldv, const void* g, const void* bias, const void* residual, long ldr, void* Y, long ldy,
+                       void* stream) {
+  if (M <= 0 || N <= 0 || (N & 7)) return AZ_ERR_ARG(164);
+  if (!V || !g || !Y || !al(V, 16) || !al(g, 16) || !al(Y, 16) || !al(bias, 16) || !al(residual, 16)) return AZ_ERR_ARG(165);
+  if ((ldv & 7) || (ldy & 7) || ldv < N || ldy < N || (residual && ((ldr & 7) || ldr < N))) return AZ_ERR_ARG(166);
+  const long groups = (long)M * (N / 8);
+  if ((groups + 255) / 256 > 0x7FFFFFF0L) return AZ_ERR_ARG(167);
+  az_launch(dora_scale_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, (hipStream_t)stream, groups, N / 8, (const bf16_t*)V, ldv, (const float*)g,
+            (const bf16_t*)bias, (const bf16_t*)residual, ldr, (bf16_t*)Y, ldy);
+  AZ_CHECK_LAUNCH();
+  return AZ_OK;
+}
+
+int az_dora_bwd_bf16(int M, int N, const void* dY, long lddy, const void* V, long ldv, const void* g, const void* inv, void* dV, long lddv,
+                     void* dm, void* workspace, long workspace_bytes, void* stream) {
+  if (M <= 0 || N <= 0 || (N & 7)) return AZ_ERR_ARG(168);
+  if (!dY || !g || !dV || !al(dY, 16) || !al(g, 16) || !al(dV, 16)) return AZ_ERR_ARG(169);
+  if (dm && (!V || !inv || !workspace || !al(V, 16) || !al(inv, 4) || !al(dm, 2) || !al(workspace, 4))) return AZ_ERR_ARG(169);
+  if ((lddy & 7) || (lddv & 7) || lddy < N || lddv < N || (dm && ((ldv & 7) || ldv < N))) return AZ_ERR_ARG(170);
+  // rows per split: about 1024 workgroups in all, at most 64 splits, whole groups of 8 rows, and partials that fit the workspace
+  const long cb = ((long)N + 255) / 256;
+  long want = (1024 + cb - 1) / cb;
+  if (want > 64) want = 64;
+  if (dm) {
+    const long cap = workspace_bytes / ((long)N * 4);
+    if (cap < 1) return AZ_ERR_ARG(171);
+    if (want > cap) want = cap;
+  }
+  const long slices = ((long)M + 7) / 8;
+  if (want > slices) want = slices;
+  const long rps = ((slices + want - 1) / want) * 8;
+  const int nsplit = (int)(((long)M + rps - 1) / rps);
+  hipStream_t st = (hipStream_t)stream;
+  float* P = dm ? (float*)workspace : nullptr;
+  az_launch(dora_bwd_kernel, dim3((unsigned)cb, (unsigned)nsplit), dim3(256), 0, st, M, N, (int)rps, (const bf16_t*)dY, lddy, (const bf16_t*)V, ldv,
+            (const float*)g, (bf16_t*)dV, lddv, P);
+  AZ_CHECK_LAUNCH();
+  if (dm) {
+    az_launch(dora_bwd_finish_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, nsplit, (const float*)P, (const float*)inv, (bf16_t*)dm);
+    AZ_CHECK_LAUNCH();
+  }
   return AZ_OK;
 }
 

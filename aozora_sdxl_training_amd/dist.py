@@ -244,6 +244,9 @@ class ShardedRaven:
         # sit behind conv_out.bias -- on the stream that updated it, ahead of that region's W^T copies, events and gathers.
         self.lora_norm = None
         self.lora_norm_slot = None
+        # DoRA (dora.DoraState; None = off: nothing differs): step() refreshes the gains of the magnitudes at the same place -- they are read
+        # by the next FORWARD, so the pass stays on the stream that updated the adapters' region, ahead of that region's event
+        self.dora = None
 
     def master_address(self, off: int, numel: int) -> int:
         """Address of the fp32 master copy of flat [off, off + numel), which must lie inside one owned trainable range; 0 without
@@ -259,6 +262,8 @@ class ShardedRaven:
         """The max-norm pass behind the update of region i on `stream`, if i is the region that holds the adapters (the last one)."""
         if self.lora_norm is not None and i == len(self.ranges) - 1:
             self.lora_norm_slot = self.lora_norm.apply(stream)
+        if self.dora is not None and i == len(self.ranges) - 1:
+            self.dora.refresh(stream)
 
     def _make_ema(self, ema, force_local):
         if ema is None:

@@ -5,7 +5,8 @@ linears that may carry an adapter: the attention projections (the default), ever
 ResnetBlock2D ("unet": conv1 / conv2 at `conv_rank` / `conv_alpha`, kohya-ss conv_dim / conv_alpha; unet_spec.LoraSpec).
 "network_dropout", "rank_dropout" and "module_dropout" (kohya-ss's names; INTEGRATION.md "LoRA dropout") are probabilities
 in [0, 1), 0 when absent.  "scale_weight_norms" (kohya-ss's name; INTEGRATION.md "LoRA max-norm") is the limit of every module's
-|| (alpha / rank) B A ||_F, enforced after every optimizer step by lora_norm.LoraMaxNorm; absent or None = off."""
+|| (alpha / rank) B A ||_F, enforced after every optimizer step by lora_norm.LoraMaxNorm; absent or None = off.  "dora" (INTEGRATION.md
+"DoRA"; absent = off) adds a trainable magnitude `<module>.dora_scale` to every adapted linear: `<key>.dora_scale` [out][1] in the file."""
 from __future__ import annotations
 
 import json
@@ -22,6 +23,8 @@ _KEYS = ("rank", "alpha", "targets", "save_merged", "scope")
 _CONV_KEYS = ("conv_rank", "conv_alpha")        # of "scope": "unet"
 _DROP_KEYS = ("network_dropout", "rank_dropout", "module_dropout")      # kohya-ss's own names; LoraSpec.dropout, .rank_dropout, .module_dropout
 _NORM_KEY = "scale_weight_norms"               # kohya-ss's own name; LoraSpec.max_norm
+_DORA_KEY = "dora"                             # LoraSpec.dora; the file says "dora_wd": "True" in ss_network_args (LyCORIS's name, as understood)
+DORA_SUFFIX = ".dora_scale"
 DP_REFUSAL = ("LORA_PARAMS under data parallel (more than one rank): the flat gradient exchange would move the whole frozen base's "
               "gradient (5 GB at SDXL size) for a few MB of adapters; run LoRA on one GPU")
 EMA_REFUSAL = "LORA_PARAMS with \"ema_decay\": the EMA's file writer knows only the full model (EMA of adapters is a follow-up)"
@@ -69,7 +72,7 @@ def options(config, world: int = 1, ema_decay=None, cfg=None) -> Tuple[Optional[
         return None, False
     if not isinstance(hp, dict):
         raise ValueError(f"LORA_PARAMS must be a dictionary, got {type(hp).__name__}")
-    known = _KEYS + _CONV_KEYS + _DROP_KEYS + (_NORM_KEY,)
+    known = _KEYS + _CONV_KEYS + _DROP_KEYS + (_NORM_KEY, _DORA_KEY)
     unknown = sorted(k for k in hp if k not in known)
     if unknown:
         raise ValueError(f"LORA_PARAMS holds unknown key(s) {unknown}: this build reads {list(known)}")
@@ -116,13 +119,22 @@ def options(config, world: int = 1, ema_decay=None, cfg=None) -> Tuple[Optional[
             raise ValueError(f"LORA_PARAMS: conv_alpha cannot be read as a number: {conv_alpha!r}") from None
         if not conv_alpha > 0.0:
             raise ValueError(f"LORA_PARAMS: conv_alpha must be > 0, got {conv_alpha}")
+    dora = _as_bool(hp.get(_DORA_KEY, False))
+    if dora:
+        if scope == "unet":
+            raise ValueError("LORA_PARAMS: \"dora\" with \"scope\": \"unet\": the norm kernel takes no 3x3 convolution (DoRA on the convolutions is a follow-up)")
+        on = [k for k, p in zip(_DROP_KEYS, drops) if p > 0.0]
+        if on:
+            raise ValueError(f"LORA_PARAMS: \"dora\" with {on[0]}: the gain follows the unmasked up product (DoRA with dropout is a follow-up)")
+        if max_norm is not None:
+            raise ValueError(f"LORA_PARAMS: \"dora\" with {_NORM_KEY}: scaling A and B changes the row norms behind the gains (DoRA with max-norm is a follow-up)")
     if world > 1:
         raise ValueError(DP_REFUSAL)
     if ema_decay is not None:
         raise ValueError(EMA_REFUSAL)
     if scope == "unet" and conv_rank is None:
         conv_rank = rank_i              # "conv_rank" left out = "rank" (a LoraSpec of scope "unet" names it)
-    spec = LoraSpec(rank_i, alpha, str(targets), scope, conv_rank, conv_alpha, *drops, max_norm)
+    spec = LoraSpec(rank_i, alpha, str(targets), scope, conv_rank, conv_alpha, *drops, max_norm, dora=dora)
     from .unet_spec import SDXL_BASE
     lora_modules(cfg if cfg is not None else SDXL_BASE, spec)        # a target that selects nothing / something outside the scope
     return spec, _as_bool(hp.get("save_merged", False))
@@ -144,6 +156,9 @@ def file_tensors(lora_state: Dict[str, torch.Tensor], spec: LoraSpec) -> Dict[st
     a permutation of its device layout [r][kh][kw][Cin] -- and lora_up [Cout][r][1][1].  .alpha is the module's own alpha."""
     out = {}
     for name, t in lora_state.items():
+        if name.endswith(DORA_SUFFIX):           # the magnitude [out] as a column [out][1]
+            out[file_key(name[:-len(DORA_SUFFIX)]) + DORA_SUFFIX] = t.detach().to("cpu", torch.bfloat16).reshape(-1, 1).contiguous()
+            continue
         module, _, leaf = name.rpartition(".lora_")
         key = file_key(module)
         t = t.detach().to("cpu", torch.bfloat16)
@@ -169,6 +184,8 @@ def file_metadata(spec: LoraSpec) -> Dict[str, str]:
         args["module_dropout"] = f"{float(spec.module_dropout):g}"
     if spec.max_norm is not None:      # kohya-ss: a key of its own
         meta["ss_scale_weight_norms"] = str(float(spec.max_norm))
+    if spec.dora:
+        args["dora_wd"] = "True"
     if args:
         meta["ss_network_args"] = json.dumps(args)
     return meta
@@ -198,6 +215,9 @@ def read_lora_file(path, unet) -> Dict[str, torch.Tensor]:
         state = unet.lora_state_dict()
         want = set()
         for name in state:
+            if name.endswith(DORA_SUFFIX):
+                want.add(file_key(name[:-len(DORA_SUFFIX)]) + DORA_SUFFIX)
+                continue
             module = name.rpartition(".lora_")[0]
             want.update((file_key(module) + (".lora_down.weight" if name.endswith("A.weight") else ".lora_up.weight"), file_key(module) + ".alpha"))
         # keys the scope does not carry (a file with adapters on emb_layers, op, conv ... of a wider network): named, not dropped
@@ -205,6 +225,15 @@ def read_lora_file(path, unet) -> Dict[str, torch.Tensor]:
         if extra:
             raise KeyError(f"{Path(path).name} holds adapters this LoraSpec does not, the first of them {extra[0]} ({len(extra)} keys in all)")
         for name, mine in state.items():
+            if name.endswith(DORA_SUFFIX):
+                k = file_key(name[:-len(DORA_SUFFIX)]) + DORA_SUFFIX
+                if k not in keys:
+                    raise KeyError(f"{k} is missing from {Path(path).name} (this LoraSpec has \"dora\"; a plain LoRA file holds no magnitudes)")
+                t = f.get_tensor(k)
+                if tuple(t.shape) != (mine.numel(), 1):
+                    raise ValueError(f"{Path(path).name}: {k} has shape {tuple(t.shape)}; this LoraSpec gives {(mine.numel(), 1)}")
+                out[name] = t.reshape(tuple(mine.shape))
+                continue
             module, _, leaf = name.rpartition(".lora_")
             k = file_key(module) + (".lora_down.weight" if leaf == "A.weight" else ".lora_up.weight")
             if k not in keys:
@@ -221,7 +250,8 @@ def read_lora_file(path, unet) -> Dict[str, torch.Tensor]:
 
 def merged_state(unet) -> Dict[str, torch.Tensor]:
     """The base state dict with W + s B A in place of every adapted weight -- a 3x3 convolution: W[o][c][kh][kw] + s sum_j B[o][j]
-    A[j][c][kh][kw] -- formed in fp32 on the CPU, rounded once (by save_model).  s is the module's own alpha / rank."""
+    A[j][c][kh][kw] -- formed in fp32 on the CPU, rounded once (by save_model).  s is the module's own alpha / rank.  Under DoRA row o
+    of the sum is scaled by m[o] / || row o || (the norm in fp32 from the same fp32 sum)."""
     return merge_into({k: v.detach().cpu() for k, v in unet.state_dict().items()},
                       {k: v.detach().float().cpu() for k, v in unet.lora_state_dict().items()}, unet.lora)
 
@@ -232,7 +262,11 @@ def merge_into(sd: Dict[str, torch.Tensor], ls: Dict[str, torch.Tensor], spec: L
             module = name[:-len(".lora_A.weight")]
             W, B = sd[module + ".weight"].float(), ls[module + ".lora_B.weight"].float()
             delta = (B @ A.float().reshape(A.shape[0], -1)).reshape(W.shape)      # [o][j] x [j][c kh kw]: the logical order of both
-            sd[module + ".weight"] = W + spec.scale_of(module) * delta
+            merged = W + spec.scale_of(module) * delta
+            m = ls.get(module + DORA_SUFFIX)
+            if m is not None:
+                merged = (m.float() / merged.reshape(merged.shape[0], -1).norm(dim=1)).reshape(-1, *([1] * (merged.dim() - 1))) * merged
+            sd[module + ".weight"] = merged
     return sd
 
 

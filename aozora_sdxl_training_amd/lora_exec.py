@@ -160,13 +160,25 @@ class LoraGroup:
     Bt: torch.Tensor        # [n r][N] transposed copies, one per part
     conv3: bool = False     # the gathered products of a 3x3 convolution: the operations below need its (B, H, W)
     mids: List[int] = field(default_factory=list)     # module id per adapted part (index of <module>.weight in the parameter table): the dropout masks' key
+    # DoRA (INTEGRATION.md "DoRA"; None / empty without it): the gains of the adapted parts side by side, the names of their magnitudes
+    # (a slot of the flat buffer is padded: the gradients of adjacent parts are one vector only where N fills whole slots) and the parts
+    # of the layer that carry no adapter (they pass through with a gain of 1)
+    dg: Optional[torch.Tensor] = None        # [n N] fp32 gains g = m / norm
+    dinv: Optional[torch.Tensor] = None      # [n N] fp32 1 / norm
+    skip: List[int] = field(default_factory=list)
+    ones: Optional[torch.Tensor] = None
+    dm_names: List[str] = field(default_factory=list)
+
+    @property
+    def dora(self) -> bool:
+        return self.dg is not None
 
 
 class LoraAdapters:
     """The adapters of one AozoraUNet: views of its three flat buffers by slot, grouped per layer call and cached."""
 
     def __init__(self, slots: Dict[str, tuple], pflat, gflat, wtflat, scale_of: Callable[[str], float], trainable: Callable[[str], bool],
-                 spec=None, mid_of: Optional[Callable[[str], int]] = None):
+                 spec=None, mid_of: Optional[Callable[[str], int]] = None, dora=None):
         self.slots, self.flats, self.scale_of, self._trainable = slots, (pflat, gflat, wtflat), scale_of, trainable
         self.routes = LoraRoutes()
         # LoRA dropout (INTEGRATION.md "LoRA dropout"): (thresholds, inv) of a spec that has one, the seed of the masks, and the device
@@ -175,6 +187,7 @@ class LoraAdapters:
         self.drop = (spec.dropout_thresholds, spec.dropout_inv) if spec is not None and spec.has_dropout else None
         self.seed = 0
         self.step_word = None
+        self.dora = dora          # dora.DoraState under LoraSpec(dora=True), else None
         self._groups: Dict[tuple, Optional[LoraGroup]] = {}
 
     def group(self, mods, conv3=False) -> Optional[LoraGroup]:
@@ -199,6 +212,11 @@ class LoraAdapters:
             g = LoraGroup([p for p, _ in have], n, n == len(mods), r, N, K, self.scale_of(have[0][1]),
                           [m + sfx for _, m in have for sfx in (".lora_A.weight", ".lora_B.weight")], A, GA, At, B, GB, Bt, conv3,
                           mids=[self._mid_of(m) for _, m in have])
+            if self.dora is not None:
+                g.dg, g.dinv = self.dora.gains([m for _, m in have])
+                g.dm_names = [m + ".dora_scale" for _, m in have]
+                g.names = g.names + g.dm_names
+                g.skip, g.ones = [p for p in range(len(mods)) if p not in g.parts], self.dora.ones[:N]
         self._groups[key] = g
         return g
 
@@ -229,6 +247,37 @@ class LoraAdapters:
             return
         for i, p, n in self._launches(g):
             self.routes.up(u[:, i * g.r:(i + n) * g.r], g.B[i * g.N:(i + n) * g.N], y[:, p * g.N:(p + n) * g.N], g.s, n)
+
+    def _dm_launches(self, g):
+        """_launches for the magnitudes' gradient: a whole group in one launch only where its parts' slots are adjacent without padding."""
+        return self._launches(g) if g.N % ALIGN == 0 else [(i, p, 1) for i, p in enumerate(g.parts)]
+
+    def dora_fwd(self, g, v, y, bias=None, residual=None):
+        """y = g v (+ bias, + residual) on the column slices of the fused output (az_dora_scale_bf16); a part without an adapter passes
+        through with a gain of 1."""
+        if (bias is not None or residual is not None) and (g.n != 1 or g.skip):
+            raise AozoraError("dora: a fused projection carries neither bias nor residual")
+        N = g.N
+        for i, p, n in self._launches(g):
+            ops.dora_scale(v[:, p * N:(p + n) * N], g.dg[i * N:(i + n) * N], y[:, p * N:(p + n) * N], bias=bias, residual=residual)
+        for p in g.skip:
+            ops.dora_scale(v[:, p * N:(p + 1) * N], g.ones, y[:, p * N:(p + 1) * N])
+
+    def dora_bwd(self, g, dy, v, dv):
+        """dv = g dy and dm += inv colsum(dy v) (az_dora_bwd_bf16; dm only where the magnitude is trainable); a part without an adapter: dv = dy."""
+        N = g.N
+        for i, p, n in self._dm_launches(g):
+            # one launch writes dm of all its n parts: like dA / dB of a stacked group, a frozen part beside a trainable one receives a
+            # gradient that nobody reads (the optimizers go by the freeze mask)
+            train = any(self._trainable(nm) for nm in g.dm_names[i:i + n])
+            dm = None
+            if train:
+                o = self.slots[g.dm_names[i]][0]
+                dm = self.flats[1][o:o + n * N]
+            ops.dora_bwd(dy[:, p * N:(p + n) * N], g.dg[i * N:(i + n) * N], dv[:, p * N:(p + n) * N], v=v[:, p * N:(p + n) * N],
+                         inv=g.dinv[i * N:(i + n) * N], dm=dm)
+        for p in g.skip:
+            ops.dora_bwd(dy[:, p * N:(p + 1) * N], g.ones, dv[:, p * N:(p + 1) * N])
 
     def du(self, g, dy, du, rows_per_sample=None):
         """du_p = s dy_p B_p over the transposed copies of the up matrices, then the forward pass's masks on du."""
@@ -264,6 +313,9 @@ def wt_jobs(table, slots) -> Tuple[List[Tuple[int, int, int]], List[Tuple[int, i
     i = 0
     while i < len(table):
         o, st, _ = slots[table[i][0]]
+        if table[i][0].endswith(".dora_scale"):       # a magnitude vector: no product reads it transposed
+            i += 1
+            continue
         if math.prod(st) % ALIGN:
             raise AozoraError(f"adapter {table[i][0]} {st} does not fill whole {ALIGN}-element slots: stacked groups would not be adjacent")
         if len(st) == 4:

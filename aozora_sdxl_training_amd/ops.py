@@ -437,6 +437,75 @@ def lora_max_norm(table, max_norm, stats, stream=None):
     return stats
 
 
+# ---------------------------------------------------------------------------------------------
+# DoRA (az_dora_*)
+# ---------------------------------------------------------------------------------------------
+
+def dora_norm(table, tiles, init=False, stream=None):
+    """The row norms of W + s B A of every adapted module and their gains in ONE launch (az_dora_norm_bf16): table is the int64 DEVICE
+    job table [n][12] (dora.job_rows: addresses of W, A, B, m, g, inv; r, K, N; fp32 bits of s; first tile; 0), tiles the 64-row tiles
+    of all its rows together.  init: also write m = bf16(norm).  On `stream` (default: the current one)."""
+    _req(isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 12
+         and table.is_contiguous() and 1 <= table.shape[0] <= 65535, "dora_norm: table must be a contiguous cuda int64 [n][12], 1 <= n <= 65535")
+    _req(not isinstance(tiles, bool) and isinstance(tiles, int) and 1 <= tiles <= 0x7FFFFFF0, f"dora_norm: tiles must be a positive int, got {tiles!r}")
+    _req(isinstance(init, (bool, int)) and int(init) in (0, 1), f"dora_norm: init must be 0 or 1, got {init!r}")
+    st = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    lib().call("az_dora_norm_bf16", _ptr(table), int(table.shape[0]), int(tiles), int(init), st)
+    return table
+
+
+def _dora_gain(g, N, dev, what):
+    _req(isinstance(g, torch.Tensor) and g.is_cuda and g.device == dev and g.dtype == F32 and g.dim() == 1 and g.numel() == N and g.stride(0) == 1
+         and g.data_ptr() % 16 == 0, f"{what} must be a dense fp32 [{N}] on the activation's device, 16-byte aligned")
+
+
+def _dora_rows(t, M, N, what):
+    m, n, ld = _rows(t)
+    _req((m, n) == (M, N) and ld % 8 == 0 and t.data_ptr() % 16 == 0, f"{what} must be [{M}][{N}] with a row stride % 8 and 16-byte aligned, got {tuple(t.shape)} ld {ld}")
+    return ld
+
+
+def dora_scale(v, g, y, *, bias=None, residual=None):
+    """y = bf16(fmaf(g[o], v, bias[o] or 0) + (residual or 0)) (az_dora_scale_bf16).  v, y, residual [M][N] with their own row strides
+    (column slices of fused outputs; columns outside are untouched), g fp32 [N], bias bf16 [N]."""
+    M, N, ldv = _rows(v)
+    _req(N % 8 == 0, f"dora_scale: N {N} % 8")
+    _dora_rows(v, M, N, "dora_scale: v")
+    ldy = _dora_rows(y, M, N, "dora_scale: y")
+    _dora_gain(g, N, v.device, "dora_scale: g")
+    if bias is not None:
+        _req(bias.is_cuda and bias.dtype == BF16 and bias.dim() == 1 and bias.numel() == N and bias.stride(0) == 1 and bias.data_ptr() % 16 == 0,
+             f"dora_scale: bias must be a dense bf16 [{N}], 16-byte aligned")
+    ldr = _dora_rows(residual, M, N, "dora_scale: residual") if residual is not None else 0
+    with _prof("dora_scale" + (f" {M}x{N}" if PROFILE_SHAPES else ""), 2.0 * M * N, 2.0 * M * N * (2 + (residual is not None))):
+        lib().call("az_dora_scale_bf16", M, N, _ptr(v), ldv, _ptr(g), _ptr(bias), _ptr(residual), ldr, _ptr(y), ldy, _stream())
+    return y
+
+
+def dora_bwd(dy, g, dv, *, v=None, inv=None, dm=None):
+    """dv = bf16(g[o] dy) and, with dm, dm[o] += inv[o] sum_rows dy v in fixed order (az_dora_bwd_bf16: the partial sums go through the
+    library workspace and are finished by the same call).  dm None: dv alone (a part of a fused group that carries no adapter: g = 1)."""
+    M, N, lddy = _rows(dy)
+    _req(N % 8 == 0, f"dora_bwd: N {N} % 8")
+    _dora_rows(dy, M, N, "dora_bwd: dy")
+    lddv = _dora_rows(dv, M, N, "dora_bwd: dv")
+    _dora_gain(g, N, dy.device, "dora_bwd: g")
+    ldv, ws_ptr, ws_bytes = 0, _ptr(None), 0
+    if dm is not None:
+        _req(v is not None and inv is not None, "dora_bwd: dm needs v and inv")
+        ldv = _dora_rows(v, M, N, "dora_bwd: v")
+        _dora_gain(inv, N, dy.device, "dora_bwd: inv")
+        _req(dm.is_cuda and dm.device == dy.device and dm.dtype == BF16 and dm.dim() == 1 and dm.numel() == N and dm.stride(0) == 1,
+             f"dora_bwd: dm must be a dense bf16 [{N}]")
+        ws = workspace(dy.device)
+        ws_ptr, ws_bytes = _ptr(ws.splitk), ws.splitk.numel() * 4 - (16 << 10)        # the last 16 KiB are the GEMM core's arrival counters
+    else:
+        v = inv = None
+    with _prof("dora_bwd" + (f" {M}x{N}" if PROFILE_SHAPES else ""), 3.0 * M * N, 2.0 * M * N * (2 + (dm is not None))):
+        lib().call("az_dora_bwd_bf16", M, N, _ptr(dy), lddy, _ptr(v), ldv, _ptr(g), _ptr(inv), _ptr(dv), lddv, _ptr(dm), ws_ptr, ws_bytes, _stream())
+    return dv
+
+
 def lora_wgrad(small, big, out, *, parts=1, scale=1.0, accumulate=True, small_major=True):
     """out (+)= scale * small_p^T @ big_p, summed over the rows (az_lora_wgrad_bf16).  small [M][parts * ns] (du or u), big [M][parts * nb]
     (x or dy).  small_major: out [parts * ns][nb] (dA_cat = du^T x); else out [parts * nb][ns] (the stacked dB_p = s dy_p^T u_p)."""

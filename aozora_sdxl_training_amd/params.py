@@ -337,7 +337,8 @@ class ParamStore:
         return self.owner
 
     def init_lora(self, seed: int):
-        """B = 0; A ~ U(-1/sqrt(K), 1/sqrt(K)) (K = the fan-in: 9 Cin for a 3x3 convolution) drawn on the CPU from one generator seeded with `seed`, in table order."""
+        """B = 0; A ~ U(-1/sqrt(K), 1/sqrt(K)) (K = the fan-in: 9 Cin for a 3x3 convolution) drawn on the CPU from one generator seeded with `seed`, in table order.
+        A DoRA magnitude is written as 0 here; AozoraUNet.init_lora sets it to the row norms behind this (dora.DoraState.refresh(init=True))."""
         g = torch.Generator().manual_seed(int(seed))
         sd = {}
         for name, shape in self._table[len(self._base_table):]:

@@ -40,7 +40,8 @@ _KERNEL_ENTRIES = frozenset({
     "az_scale_f32", "az_stage_inputs", "az_adamw8bit_step", "az_ema_flat", "az_adamw_flat_master", "az_robust_loss_fwd_bwd", "az_adamw_flat_seg",
     "az_noise_shape", "az_noise_target_ex", "az_prodigy_begin", "az_prodigy_moments", "az_prodigy_finish", "az_prodigy_apply",
     "az_lora_down_bf16", "az_lora_up_bf16", "az_lora_wgrad_bf16", "az_lora_up_geglu_bf16",
-    "az_lora_conv_down_bf16", "az_lora_conv_dgrad_bf16", "az_lora_conv_wgrad_bf16", "az_lora_dropout_bf16", "az_lora_max_norm_bf16"})
+    "az_lora_conv_down_bf16", "az_lora_conv_dgrad_bf16", "az_lora_conv_wgrad_bf16", "az_lora_dropout_bf16", "az_lora_max_norm_bf16",
+    "az_dora_norm_bf16", "az_dora_scale_bf16", "az_dora_bwd_bf16"})
 # ... and the ones with a stream argument that end in something else (graph capture / launch, event and stream calls, copies)
 _NOT_KERNEL_ENTRIES = frozenset({"az_graph_begin", "az_graph_end", "az_graph_launch", "az_event_record", "az_stream_wait_event",
                                  "az_stream_sync", "az_memset_async", "az_memcpy_async", "az_titan_offload"})

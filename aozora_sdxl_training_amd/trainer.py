@@ -240,17 +240,19 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
         excl = [k.strip() for k in excl.split(",") if k.strip()]
     lora_drop = lora_spec is not None and lora_spec.has_dropout
     if lora_spec is not None:        # the whole base frozen, every adapter trainable: one contiguous range of the flat buffers
+        adapter_names = set(unet.lora_state_dict())          # A, B and, under DoRA, the magnitudes
         for n, p in unet.named_parameters():
-            p.requires_grad = ".lora_" in n
+            p.requires_grad = n in adapter_names
         if lora_drop:                # the masks are a function of (SEED, global micro-step): nothing of them goes into a training state
             unet.set_lora_dropout_seed(config.SEED)
         if rank == 0:
-            n_ad = sum(p.numel() for n, p in unet.named_parameters() if ".lora_" in n)
+            n_ad = sum(p.numel() for n, p in unet.named_parameters() if n in adapter_names)
             drops = (f", dropout {lora_spec.dropout:g} / rank_dropout {lora_spec.rank_dropout:g} / module_dropout {lora_spec.module_dropout:g}"
                      if lora_drop else "")
             n_conv = sum(n.endswith(".lora_A.weight") and p.dim() == 4 for n, p in unet.named_parameters())
+            n_lin = sum(n.endswith(".lora_A.weight") for n in adapter_names) - n_conv
             convs = f" and {n_conv} adapted 3x3 convolutions at conv_rank {lora_spec.conv3_rank}, conv_alpha {lora_spec.conv3_alpha:g}" if n_conv else ""
-            print(f"INFO: LoRA is ON (rank {lora_spec.rank}, alpha {lora_spec.alpha:g}, scope {lora_spec.scope}{drops}, {len(unet.lora_state_dict()) // 2 - n_conv} adapted linears{convs}, {n_ad} "
+            print(f"INFO: LoRA is ON (rank {lora_spec.rank}, alpha {lora_spec.alpha:g}, scope {lora_spec.scope}{drops}, {n_lin} adapted linears{convs}, {n_ad} "
                   f"trainable elements{', merged model saved too' if lora_merged else ''}): an option outside the reference; the base is frozen, "
                   "UNET_EXCLUDE_TARGETS is not applied, and every model file holds the adapters alone (kohya-ss layout)")
     else:
@@ -345,6 +347,16 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
             print(f"INFO: LoRA max-norm is ON (scale_weight_norms {lora_spec.max_norm:g}, {lora_norm.n} modules in one launch per optimizer step"
                   f"{', fp32 masters scaled with them' if lora_norm.has_master else ''}): an option outside the reference; written from kohya-ss's "
                   "rule as understood, unpinned against the package")
+    # LORA_PARAMS "dora" (dora.py; absent = off: no launch, no buffer): the gains of the magnitudes are derived state that the forward reads;
+    # one launch behind every optimizer step's update of the adapters, at the place of the max-norm pass.  The magnitudes were set to the
+    # row norms when the adapters were drawn (lora.load_unet), ahead of the optimizer: its fp32 masters hold them.
+    dora = unet.dora if lora_spec is not None and lora_spec.dora else None
+    if dora is not None:
+        if flat_opt:
+            optimizer.dora = dora
+        if rank == 0:
+            print(f"INFO: DoRA is ON ({dora.n} magnitude vectors, {dora.g.numel()} elements; their gains are refreshed in one launch per optimizer "
+                  "step): an option outside the reference; this project's own contract, unpinned against peft / LyCORIS")
     lr_scheduler = CustomCurveLRScheduler(optimizer, config.LR_CUSTOM_CURVE, config.MAX_TRAIN_STEPS)
     if getattr(config, "RESUME_TRAINING", False):
         if dp:       # every rank resumes its own shard (written next to rank 0's training-state file)
@@ -575,6 +587,8 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
                         else:
                             norm_slot = lora_norm.apply()         # same stream, right behind the step; the W^T copies follow the scaled values
                             unet.mark_params_dirty()
+                    if dora is not None and not flat_opt:
+                        dora.refresh()                            # same stream, right behind the step: the next forward reads the new gains
                     optimizer.zero_grad(set_to_none=True)
                     optimizer_step += 1
                     if prodigy:                     # (this branch has already blocked on the norm's .item())

@@ -234,7 +234,13 @@ class AozoraUNet:
             setattr(self, k, getattr(P, k))      # never rebound: the same objects under the names the layers, optimizers and tools read
         # the adapter executor (lora_exec.py): groups, routing rules and the four per-group operations linear() / conv() call
         mids = {n[:-len(".weight")]: i for i, (n, _) in enumerate(self._base_table) if n.endswith(".weight")}
-        self.adapters = (LoraAdapters(self._slots, self.pflat, self.gflat, self.wtflat, lora.scale_of, self._trainable, lora, mids.__getitem__)
+        # DoRA (dora.py): the fp32 gains of the magnitudes, derived state that the FORWARD reads -- refreshed behind every parameter change
+        self.dora = None
+        if lora is not None and lora.dora:
+            from .dora import DoraState
+            self.dora = DoraState(self)
+        self.adapters = (LoraAdapters(self._slots, self.pflat, self.gflat, self.wtflat, lora.scale_of, self._trainable, lora, mids.__getitem__,
+                                      dora=self.dora)
                          if lora is not None else None)
         self._step_B = 1              # samples of the current step (forward_nhwc): rows / B = the rows of one sample, for rank dropout
         self._pools: Dict[tuple, _Pool] = {}
@@ -297,10 +303,17 @@ class AozoraUNet:
     def named_parameters(self): return self.params.named_parameters()
     def parameters(self): return self.params.parameters()
     def state_dict(self): return self.params.state_dict()
-    def load_state_dict(self, sd, strict=True): return self.params.load_state_dict(sd, strict)
+    def load_state_dict(self, sd, strict=True): return self._dora_refreshed(self.params.load_state_dict(sd, strict), base=True)
     def lora_state_dict(self): return self.params.lora_state_dict()
-    def load_lora_state_dict(self, sd): return self.params.load_lora_state_dict(sd)
-    def init_lora(self, seed): return self.params.init_lora(seed)
+    def load_lora_state_dict(self, sd): return self._dora_refreshed(self.params.load_lora_state_dict(sd))
+    def init_lora(self, seed): return self._dora_refreshed(self.params.init_lora(seed), init=True)
+
+    def _dora_refreshed(self, ret, init=False, base=False):
+        """Behind a load: the gains of the DoRA magnitudes follow the new W, A, B, m (init: the magnitudes become the row norms first).
+        A load of the base before any adapters exist (base) issues nothing: there is no magnitude to form a gain from yet."""
+        if self.dora is not None and (self.dora.launches or not base):
+            self.dora.refresh(init=init)
+        return ret
     def trainable_ranges(self): return self.params.trainable_ranges()
     def expose_grads(self): return self.params.expose_grads()
     def zero_grad(self, set_to_none=True): return self.params.zero_grad(set_to_none)
@@ -654,7 +667,19 @@ class AozoraUNet:
         lg = None
         if self.adapters is not None:
             lg = self.adapters.group(lora_mods if lora_mods is not None else ([wname[:-len(".weight")]] if wname else []))
-        if pre is not None:
+        dora = lg is not None and lg.dora
+        if dora:
+            # DoRA (INTEGRATION.md "DoRA"): v = the base product WITHOUT bias and residual (a hoisted one: `pre`), the up product on v in
+            # place, then y = g v + bias + residual; v is kept for the backward.  The GEGLU follows on y: no fused form.
+            v = pre if pre is not None else self._new(rows, N, need_grad=False)
+            y = out if out is not None else self._new(rows, N)
+            if pre is None:
+                ops.gemm(x.t, W, v.t, trans_b=True, split_k=0 if (rows <= 512 and residual is None) else 1)
+            u, l_train = self._adapter_fwd(lg, x, v)
+            self.adapters.dora_fwd(lg, v.t, y.t, self._w[bname] if bname else None, residual.t if residual is not None else None)
+            if geglu_out is not None:
+                ops.geglu_fwd(y.t, geglu_out.t)
+        elif pre is not None:
             y = pre
         else:
             y = out if out is not None else self._new(rows, N)
@@ -666,7 +691,7 @@ class AozoraUNet:
                 ops.gemm(x.t, W, y.t, trans_b=True, bias=self._w[bname] if bname else None,
                          residual=residual.t if residual is not None else None,
                          split_k=0 if (rows <= 512 and residual is None) else 1)
-        if lg is not None:      # the adapter follows the base product (a hoisted one: here, at the layer's own place on the tape)
+        if lg is not None and not dora:      # the adapter follows the base product (a hoisted one: here, at the layer's own place on the tape)
             u, l_train = self._adapter_fwd(lg, x, y, geglu_out=geglu_out)
 
         def bwd():
@@ -674,13 +699,27 @@ class AozoraUNet:
             if dy is None:
                 return
             du = self._adapter_du_buf(lg, x)
+            # DoRA: every consumer of dy but the bias and the residual reads dv = g dy (pool order independent of the freeze mask)
+            dyv = self._pool.get(tuple(dy.shape), BF16) if dora else dy
             on_side = side_dgrad and self.policy.temb_side and self.concurrent_wgrad and len(self._sides) == 1
+            if dora and on_side:      # dy would be produced on the branch and read by az_dora_bwd_bf16 on the chain, unordered
+                raise AozoraError("DoRA on a layer whose data gradient runs on the parameter-gradient branch (side_dgrad) is not supported")
             if on_side:
                 y.ready = None      # written on the branch, read on the branch
             else:
                 self._wait_ready(y)
             b_train = bname is not None and self._trainable(bname)
             job = (dy, x.t, GW, self._gw[bname] if b_train else None)
+            if dora:
+                # dv = g dy and the magnitude's gradient, ahead of every reader of dv: on the chain where the input has a gradient, else
+                # (the text context: dy may itself be produced on the branch) on the branch, in order ahead of the weight gradients
+                if x.need_grad:
+                    self.adapters.dora_bwd(lg, dy, v.t, dyv)
+                elif l_train or w_train:
+                    self._side_defer(lambda: self.adapters.dora_bwd(lg, dy, v.t, dyv))
+                job = (dyv, x.t, GW, None)       # a trainable base weight takes dv; its bias the layer's own dy
+                if w_train and b_train:
+                    self._side_defer(lambda: self._bias_grad(dy, bname, N))
 
             def wgrad():        # parameter gradients run as a free-running branch beside the data-gradient chain
                 if w_train:
@@ -699,13 +738,13 @@ class AozoraUNet:
             elif w_train or b_train:
                 self._side_defer(wgrad)
             if lg is not None:
-                self._adapter_bwd(lg, l_train, x, u, dy, du)
+                self._adapter_bwd(lg, l_train, x, u, dyv, du)
             if x.need_grad:
                 dx, add = self._gbuf(x)
                 oop = add is not None and add is not dx
 
                 def dgrad():
-                    ops.gemm(dy, WT, dx, trans_b=True, accumulate=add is dx, residual=add if oop else None,      # dX = dY . W  as  dY . (W^T)^T
+                    ops.gemm(dyv, WT, dx, trans_b=True, accumulate=add is dx, residual=add if oop else None,      # dX = dY . W  as  dY . (W^T)^T
                              split_k=0 if (rows <= 512 and not oop) else 1)
                     if lg is not None:
                         self.adapters.dgrad(lg, du.t, dx)         # dx += du A_cat, directly behind the base product
@@ -1264,6 +1303,10 @@ class AozoraUNet:
 
         skips: List[Act] = []
         level_geom = [geom]      # geometry of every level on the way down: the up path's upsamplers return to exactly these
+        if self.dora is not None:
+            # the magnitudes and their gains lie behind conv_out.bias (region 2: updated on the background stream, the norm pass behind it)
+            # and are read from the first transformer of the down path on: their region's event is taken up front
+            self._live(self.wait_region_params, 2)
         h, _ = self.conv(xin, geom, "conv_in.weight", "conv_in.bias", out=skip_dest(B * H * W_, ch[0]))
         self._hoist_shared_input_linears(self._region_blocks(0), ctx_a, emb_s)
         skips.append(h)

@@ -173,7 +173,9 @@ class LoraSpec:
     read by the freeze keywords' rule (fnmatch(name, kw if '*' in kw else '*kw*')) against the module names of the scope; '' or
     '*' = all.  dropout / rank_dropout / module_dropout: kohya-ss network, rank and module dropout of the adapters' inner activation, each
     a probability in [0, 1) (INTEGRATION.md "LoRA dropout"); all three 0 (the default) = off, and such a spec equals one built without them.
-    max_norm: kohya-ss scale_weight_norms, the limit of every module's || scale B A ||_F (INTEGRATION.md "LoRA max-norm"); None = off."""
+    max_norm: kohya-ss scale_weight_norms, the limit of every module's || scale B A ||_F (INTEGRATION.md "LoRA max-norm"); None = off.
+    dora: weight-decomposed LoRA (INTEGRATION.md "DoRA"): every adapted linear also carries a trainable magnitude `<module>.dora_scale`
+    [out]; False (the default) = off, and such a spec equals one built without it.  Not with scope "unet", dropout or max_norm."""
     rank: int = 16
     alpha: float = 16.0
     targets: str = ""
@@ -187,6 +189,9 @@ class LoraSpec:
     # LoRA max-norm (INTEGRATION.md "LoRA max-norm"; kohya-ss scale_weight_norms): the limit of || (alpha / rank) B A ||_F per module,
     # enforced after every optimizer step; None (the default) = off, and such a spec equals one built without it
     max_norm: Optional[float] = None
+    # DoRA (INTEGRATION.md "DoRA"; Liu et al., arXiv 2402.09353): a trainable per-output-channel magnitude beside every adapter; False
+    # (the default) = off, and such a spec equals one built without it
+    dora: bool = False
 
     def __post_init__(self):
         if self.max_norm is not None:
@@ -212,6 +217,11 @@ class LoraSpec:
             raise ValueError(f"LoRA conv_alpha must be > 0, got {self.conv_alpha!r}")
         if (self.conv_rank is not None or self.conv_alpha is not None) and self.scope != "unet":
             raise ValueError(f"LoRA conv_rank / conv_alpha belong to scope \"unet\" (scope {self.scope!r} adapts no convolution)")
+        if not isinstance(self.dora, bool):
+            raise ValueError(f"LoRA dora must be True or False, got {self.dora!r}")
+        if self.dora and (self.scope == "unet" or self.max_norm is not None or self.has_dropout):
+            raise ValueError("LoRA dora goes with scope \"attention\" or \"transformer\" and without dropout or max_norm (DoRA on the "
+                             "convolutions, with dropout and with max-norm are follow-ups)")
 
     @property
     def scale(self) -> float:
@@ -298,7 +308,8 @@ def lora_table(cfg: UNetConfig, spec: LoraSpec):
     """[(name, shape)] of the adapter parameters, appended behind conv_out.bias in the parameter-table order of their modules.  Per
     attention, the down matrices A [r][in] of its fused group first (adjacent: one stacked operand), then the group's up matrices
     B [out][r], then to_out.0 (attn2: to_q first).  Every other linear of scope "transformer" (proj_in, ff.net.0.proj, ff.net.2,
-    proj_out) is A, then B, at its module's place, and so are conv1, conv2 and conv_shortcut of scope "unet"."""
+    proj_out) is A, then B, at its module's place, and so are conv1, conv2 and conv_shortcut of scope "unet".  With spec.dora the
+    magnitudes `<module>.dora_scale` (out,) of a group follow its up matrices, in the group's part order."""
     shapes = dict(param_table(cfg))
     order = lora_modules(cfg, spec)
     mods = set(order)
@@ -318,4 +329,6 @@ def lora_table(cfg: UNetConfig, spec: LoraSpec):
                 shp = shapes[n + ".weight"]
                 out.append((n + ".lora_A.weight", (spec.rank_of(n), shp[1]) + (tuple(shp[2:]) if lora_is_conv3(n) else ())))
             out += [(n + ".lora_B.weight", (shapes[n + ".weight"][0], spec.rank_of(n))) for n in names]
+            if spec.dora:
+                out += [(n + ".dora_scale", (shapes[n + ".weight"][0],)) for n in names]
     return out

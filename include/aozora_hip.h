@@ -663,6 +663,42 @@ int az_lora_dropout_bf16(int rows, int r, int parts, int rows_per_sample, void* 
 /* ref: not in the reference (train.py is full fine-tuning only); kohya-ss networks/lora.py apply_max_norm_regularization */
 int az_lora_max_norm_bf16(const void* jobs_dev, int n_modules, float max_norm, void* stats, void* stream);
 
+/* ---- DoRA: weight-decomposed LoRA (Liu et al., arXiv 2402.09353; INTEGRATION.md "DoRA"; tests/dora_ref.py restates it in float64
+ *      and in the rounded steps below) ----------------------------------------------------------------------------------------
+ * An adapted linear W[N][K], A[r][K], B[N][r], s = alpha / r carries a trainable magnitude m[N] (bf16).  bf16 in memory, sums in fp32:
+ *     once per parameter change   n2[o] = sum_k fmaf(s, sum_j B[o][j] A[j][k], float(W[o][k]))^2      (direct form: no cancellation)
+ *                                 inv[o] = 1 / sqrtf(n2[o])        g[o] = float(m[o]) * inv[o]         (fp32 vectors, derived state)
+ *     forward    v = bf16(x W^T), v = bf16(float(v) + s (u B^T)) (az_lora_up_bf16), y = bf16(fmaf(g[o], float(v), bias[o] or 0) + (float(residual) or 0))
+ *     backward   dv = bf16(g[o] * float(dy))       dm[o] = bf16(fmaf(inv[o], sum_rows float(dy[row][o]) float(v[row][o]), float(dm[o])))
+ * The norm is a constant of the backward (the paper's section 4.3).  No floating-point atomics: every sum has one fixed order.
+ *
+ * az_dora_norm_bf16: ONE launch serves every module.  jobs_dev is a DEVICE table of n_modules rows of twelve 64-bit words: the addresses
+ *   of W, A, B, m, g, inv; r, K, N; the fp32 bits of s in the low half; the index of the module's first tile (a tile = 64 output rows;
+ *   ascending over the table); one unused word.  `tiles` = the tiles of all rows together = the grid.  A workgroup owns a tile and walks
+ *   K: the B A tile on v_mfma_f32_16x16x32_bf16 (rank padded by zero fragments), plus W, squared and accumulated per row.  init = 1
+ *   also writes m[o] = bf16(sqrtf(n2[o])) (then g = float(m) inv is within 2^-8 of 1 -- bf16 keeps 8 significant bits -- and not exactly 1); init = 0 only reads m.  r is one
+ *   of 4, 8, 16, 32, 64; K and N positive multiples of 8 up to 2^24; W, A, B 16-byte aligned and dense ([N][K], [r][K], [N][r]: a 3x3
+ *   convolution is not accepted), m 2-byte, g and inv 4-byte aligned.  A row that breaks one of these is skipped by its workgroups:
+ *   nothing of W, A, B, m is read or written, and g, inv of the tile's rows are set to NaN where their addresses and N are themselves
+ *   well-formed (else nothing at all is touched).  Argument errors, nothing launched: jobs_dev null or not 8-byte aligned (-1160);
+ *   n_modules outside [1, 65535] (-1161); tiles outside [1, 2^31 - 16] (-1162); init not 0 or 1 (-1163).
+ * az_dora_scale_bf16: Y[M][N] (row stride ldy) from V (ldv), the fp32 gains g[N], bias[N] or NULL, residual (ldr) or NULL, by the
+ *   forward rule above -- one fmaf, then the residual's add, then one rounding.  Columns at and beyond N are never touched: Y, V may be
+ *   column slices of fused outputs.  N % 8 == 0; every pointer 16-byte aligned, every row stride a multiple of 8 and >= N.  Errors:
+ *   M, N (-1164); a null or misaligned pointer (-1165); a row stride (-1166); more than 2^31 - 16 workgroups (-1167).
+ * az_dora_bwd_bf16: one pass over dY (and V): dV by the rule above and, with dm != NULL, fp32 partial column sums of dY * V per row
+ *   range in `workspace` (at most 64 ranges, a function of the shapes and workspace_bytes only; N floats per range, -1171 when not even
+ *   one fits), then a finish on the same stream that adds them in ascending order and accumulates into dm.  dm == NULL: dV only (V, inv
+ *   and workspace are not read).  Same alignment rules as the forward.  Errors: M, N (-1168); pointers (-1169); strides (-1170). */
+/* ref: not in the reference (train.py is full fine-tuning only); arXiv 2402.09353 section 4, peft's DoraLinearLayer.get_weight_norm */
+int az_dora_norm_bf16(const void* jobs_dev, int n_modules, long tiles, int init, void* stream);
+/* ref: not in the reference (same); follows the up product of an adapted projection */
+int az_dora_scale_bf16(int M, int N, const void* V, long ldv, const void* g, const void* bias, const void* residual, long ldr, void* Y, long ldy,
+                       void* stream);
+/* ref: not in the reference (same); in front of the adapter's and the base layer's gradients in the backward of train.py:2765 */
+int az_dora_bwd_bf16(int M, int N, const void* dY, long lddy, const void* V, long ldv, const void* g, const void* inv, void* dV, long lddv,
+                     void* dm, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- native launch tape: the executor seam (SURVEY.md 8b "az_unet_step") ----------------------------------------------------
  * The step's launch sequence is static (same entry points, pointers, streams and events every step of a resolution bucket).  The
  * host executor records it once; az_tape_play re-issues it from C: entry-point calls (arguments as 64-bit words: int / long by

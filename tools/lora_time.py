@@ -20,7 +20,14 @@
             (With LoRA off this tree issues the parent commit's launches: profiles/lora_bench_ab.json and lora_ff_bench_ab.json hold
             the alternated bench.py runs of the builds.)
 
-    python tools/lora_time.py [--reps 9] [--inner 200] [--no-kernels] [--no-geglu] [--no-step] [--out FILE]
+  dora:     (--dora: this leg alone; profiles/dora_time.json) the three az_dora_* kernels at the shapes above and at the two GEGLU
+            projections [M][2 H] -- az_dora_norm_bf16 on a one-module table, az_dora_scale_bf16 with bias and residual,
+            az_dora_bwd_bf16 with the magnitude's gradient -- each as a native launch tape, `reps` repetitions dealt round-robin over
+            the kernels; the norm pass over all modules of scope "attention" and "transformer" at SDXL size, rank 16; and one micro-step
+            at 1024^2, B = 4, rank 16 with DoRA against plain LoRA of this tree for both scopes, alternated in one process, with the
+            launches each records.
+
+    python tools/lora_time.py [--reps 9] [--inner 200] [--no-kernels] [--no-geglu] [--no-step] [--dora] [--out FILE]
                                                                                      -> one JSON line (also written to FILE)"""
 import argparse
 import json
@@ -173,6 +180,116 @@ def step_ab(rounds, per_round):
     return res
 
 
+def _sdxl_unet(spec):
+    from bench import init_weights_on_device
+    from aozora_sdxl_training_amd.unet import AozoraUNet
+    from aozora_sdxl_training_amd.unet_spec import SDXL_BASE
+    unet = AozoraUNet(SDXL_BASE, DEV, lora=spec)
+    init_weights_on_device(unet)
+    adapters = set(unet.lora_state_dict())
+    g = torch.Generator(device=DEV).manual_seed(3)
+    with torch.no_grad():
+        for n, p in unet.named_parameters():
+            p.requires_grad = n in adapters
+            if n.endswith(".lora_A.weight"):
+                p.copy_((torch.randn(p.shape, generator=g, device=DEV) * 0.02).bfloat16())
+    if spec.dora:
+        unet.dora.refresh(init=True)        # B = 0: the magnitudes are the base weight's row norms
+    return unet
+
+
+def dora_kernels(reps, inner):
+    """us per call of the three az_dora_* entry points (median and spread over `reps`, the kernels taking turns)."""
+    from aozora_sdxl_training_amd import dora, ops
+    from aozora_sdxl_training_amd.lora_norm import s_bits
+    g = torch.Generator(device=DEV).manual_seed(2)
+    rnd = lambda *s: (torch.randn(*s, generator=g, device=DEV) * 0.05).bfloat16()
+    side = lambda t: dict(median_us=round(statistics.median(t), 2), spread_us=round(max(t) - min(t), 2))
+    shapes = SHAPES + [(f"{label} (N = 2 H)", M, 1280 if H == 5120 else 640, 2 * H) for label, M, H in GEGLU_SHAPES]
+    out = {}
+    for label, M, K, N in shapes:
+        for r in RANKS:
+            W, A, B, m = rnd(N, K), rnd(r, K), rnd(N, r), rnd(N)
+            gg, inv = torch.ones(N, device=DEV), torch.ones(N, device=DEV)
+            row = [W.data_ptr(), A.data_ptr(), B.data_ptr(), m.data_ptr(), gg.data_ptr(), inv.data_ptr(), r, K, N, s_bits(1.0), 0, 0]
+            dora.check_row(row)
+            table, tiles = torch.tensor([row], dtype=torch.int64, device=DEV), (N + dora.TILE_ROWS - 1) // dora.TILE_ROWS
+            v, y, res, bias, dy, dv, dm = rnd(M, N), rnd(M, N), rnd(M, N), rnd(N), rnd(M, N), rnd(M, N), rnd(N)
+            tapes = {"norm (one module)": taped(lambda: ops.dora_norm(table, tiles, False), inner)[0],
+                     "scale": taped(lambda: ops.dora_scale(v, gg, y, bias=bias, residual=res), inner)[0],
+                     "bwd": taped(lambda: ops.dora_bwd(dy, gg, dv, v=v, inv=inv, dm=dm), inner)[0]}
+            times = {k: [] for k in tapes}
+            for t in tapes.values():
+                timed(t, inner)
+            for _ in range(reps):
+                for k, t in tapes.items():
+                    times[k].append(timed(t, inner))
+            out[f"{label} r={r}"] = {k: side(v_) for k, v_ in times.items()}
+            if r == RANKS[0]:       # scale and bwd do not see the rank
+                out[f"{label} r={r}"]["bytes_scale"] = 2 * M * N * 3
+    return out
+
+
+def dora_norm_pass(reps, inner):
+    """az_dora_norm_bf16 over every module of a scope at SDXL size, rank 16: us per pass, modules, rows, bytes of W read."""
+    from aozora_sdxl_training_amd.unet_spec import LoraSpec
+    out = {}
+    for scope in ("attention", "transformer"):
+        unet = _sdxl_unet(LoraSpec(16, 16.0, "", scope, dora=True))
+        tape = taped(lambda: unet.dora.refresh(), inner)[0]
+        timed(tape, inner)
+        t = [timed(tape, inner) for _ in range(reps)]
+        w_bytes = sum(2 * int(row[7]) * int(row[8]) for row in unet.dora.table.cpu().tolist())
+        out[scope] = dict(median_us=round(statistics.median(t), 1), spread_us=round(max(t) - min(t), 1), modules=unet.dora.n,
+                          rows=int(unet.dora.g.numel()), tiles=unet.dora.tiles, base_weight_bytes_read=w_bytes,
+                          GB_per_s=round(w_bytes / statistics.median(t) / 1e3, 1))
+        del unet, tape
+        torch.cuda.empty_cache()
+    return out
+
+
+def dora_step_ab(rounds, per_round):
+    """One micro-step at 1024^2, B = 4, rank 16: DoRA against plain LoRA of this tree, both scopes, alternated in one process."""
+    from bench import synthetic_batch
+    from aozora_sdxl_training_amd._lib import Call
+    from aozora_sdxl_training_amd.train_step import TrainStep
+    from aozora_sdxl_training_amd.unet_spec import LoraSpec
+    batch = synthetic_batch(0, 0, 0, 4, DEV)
+    sides = {}
+    for name, spec in (("lora", LoraSpec(16, 16.0)), ("dora", LoraSpec(16, 16.0, dora=True)),
+                       ("lora_transformer", LoraSpec(16, 16.0, "", "transformer")), ("dora_transformer", LoraSpec(16, 16.0, "", "transformer", dora=True))):
+        unet = _sdxl_unet(spec)
+        step = TrainStep(unet, mode="epsilon", grad_accum=1, world_size=1, use_graph=False)
+        for _ in range(3):          # pool allocation, tape recording, first replay
+            step.micro_step(*batch)
+        step.synchronize()
+        unet.zero_grad()
+        sides[name] = (unet, step)
+    times = {k: [] for k in sides}
+    for _ in range(rounds):
+        for name, (unet, step) in sides.items():
+            step.micro_step(*batch); step.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(per_round):
+                step.micro_step(*batch)
+            step.synchronize()
+            times[name].append((time.perf_counter() - t0) * 1e3 / per_round)
+            unet.zero_grad()
+    res = {k: dict(median_ms=round(statistics.median(v), 3), spread_ms=round(max(v) - min(v), 3)) for k, v in times.items()}
+    launches, act = {}, {}
+    for name, (unet, step) in sides.items():
+        tapes = [bk.tape for bk in step._buckets.values() if getattr(bk, "tape", None) is not None]
+        launches[name] = sum(1 for op in tapes[0] if isinstance(op, Call) and op.name != "az_set_launch_stop_event") if tapes else None
+        act[name] = max(unet.activation_bytes()["need"].values())
+    res["launches_per_micro_step"] = launches
+    res["activation_bytes"] = act
+    for scope in ("", "_transformer"):
+        a, b = res["lora" + scope], res["dora" + scope]
+        res["dora_over_lora" + scope] = round(b["median_ms"] / a["median_ms"], 4)
+        res["dora_slower_beyond_spread" + scope] = bool(b["median_ms"] - a["median_ms"] > max(a["spread_ms"], b["spread_ms"]))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
@@ -182,11 +299,20 @@ def main():
     ap.add_argument("--no-step", action="store_true")
     ap.add_argument("--no-kernels", action="store_true")
     ap.add_argument("--no-geglu", action="store_true")
+    ap.add_argument("--dora", action="store_true", help="the DoRA leg alone (profiles/dora_time.json)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("lora_time needs a GPU")
     rep = dict(tool="tools/lora_time.py", device=torch.cuda.get_device_name(0))
+    if a.dora:
+        rep["procedure"] = f"native launch tapes of {a.inner} launches, {a.reps} repetitions, sides taking turns in one process; spread = max - min of one side"
+        if not a.no_kernels:
+            rep["dora_kernels_us"] = dora_kernels(a.reps, a.inner)
+            rep["dora_norm_pass_sdxl_rank16"] = dora_norm_pass(a.reps, max(1, a.inner // 10))
+        if not a.no_step:
+            rep["micro_step_1024_B4_rank16"] = dora_step_ab(a.rounds, a.per_round)
+        a.no_kernels = a.no_geglu = a.no_step = True
     if not a.no_kernels:
         rep["kernels"] = kernels(a.reps, a.inner)
     if not a.no_geglu:
