@@ -186,6 +186,9 @@ enum AzOption {
   AZ_OPT_GN_RPT_BWD,          // ... the same for the backward's passes.  More rows = fewer, longer-lived blocks: beside the weight-gradient stream a
                               //    light kernel pays for every block slot it has to wait for (profiles/r05_dilation_in_step.txt)
   AZ_OPT_GN_RPT_APPLY,        // ... and for the backward's element-wise pass (dx), whose chunks are independent of the partial sums'
+  AZ_OPT_CONVWG_STRIP,        // 1: 3x3 stride-1 convolution weight gradients on grids whose 64-pixel k-tiles are whole rows or an aligned part of one
+                              //    (W % 64 == 0 or 64 % W == 0, W >= 8, H * W % 64 == 0, Cin % 32 == 0, Cout >= 64) stage ONE halo strip of X for all nine taps
+                              //    (az_gemm_strip.inc); 0: the per-tap gather of gemm_kernel<A_COL, B_CONVWG>.  Same bits at equal split_k.
   AZ_OPT_COUNT
 };
 int az_opt(int id);           // host side

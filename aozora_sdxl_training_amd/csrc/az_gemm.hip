@@ -15,6 +15,7 @@
 // Layout: activations are NHWC (B,H,W,C) == row-major [pixels][C]; conv weights [Cout][ky][kx][Cin].
 // Tiles (BM x BN x 64, 8 or 16 waves): 128x128 (8 waves of 32x64, 2 workgroups / CU: every weight gradient),
 // 128x160 (8 waves of 32x80; 2 stages, or 3 stages in the exclusive forward pass), 256x256 (16 waves of 64x64, 1 workgroup / CU);
+// the 3x3 stride-1 convolution weight gradients of whole-row k-tiles have a kernel of their own (az_gemm_strip.inc: 128 x (9 taps x 32));
 // v_mfma_f32_16x16x32_bf16 with the operands swapped (D^T = W-frag x A-frag) so each lane owns 4 consecutive output columns.
 // Operand tiles reach LDS by LDS-DMA (buffer_load_dwordx4 ... lds, issued from inline asm -- see dma16s: no VGPR staging, no
 // ds_write; masked chunks use an out-of-range offset and the hardware writes zeros).
@@ -96,6 +97,7 @@ struct Params {
   // value columns n and the BN/2 gate columns H + n of the same n, arranged so that one lane owns value and gate of the same
   // element; the epilogue stores proj[M][2H] (C, needed by the backward pass) and out[M][H] = value * gelu(gate) (gg_y).
   int gg_H; bf16_t* gg_y; long gg_ldy;
+  int strip;                  // 1: 3x3 weight gradient in its strip-staged form (az_gemm_strip.inc): tiles of 128 output channels x 32 input channels x 9 taps
   Geom g;
 };
 
@@ -1087,6 +1089,8 @@ __global__ void splitk_reduce_vec_kernel(const float* __restrict__ ws, int S, lo
   }
 }
 
+#include "az_gemm_strip.inc"
+
 template <int AMODE, int BMODE, int BM, int BN, int NWM = BM / 64, int NWN = BN / 64, int NS = 2, int KB = 64, int MODE = 0>
 int launch_tile(const Params& p, hipStream_t st) {
   constexpr int LDS = NS * (BM + BN) * KB * 2 + 2048;      // + the scratch row of the rings' padding DMAs
@@ -1221,6 +1225,7 @@ int g_force_bm = 0, g_force_bn = 0, g_force_nw = 0, g_force_stages = 0;
 // family and for wgrad (split-K over pixels), which stay on 128x128 at 2 workgroups / CU.
 void choose_tile(Params& p, bool wgrad, bool b_kmajor) {
   p.nwaves = 0; p.stages = 2; p.kb = 64;
+  if (p.strip) { p.bm = SBM; p.bn = 9 * SCI; p.nwaves = 8; return; }      // (never set while a tile is forced)
   if (g_force_bm == 256 && g_force_nw == 8) {      // forced 8-wave ping-pong tile: apply_gemm8 takes it where it exists, else the 16-wave 256x256 tile
     p.bm = 256; p.bn = 256; p.nwaves = 0;
     return;
@@ -1568,7 +1573,10 @@ static int conv_impl(int mode, int batch, int Hin, int Win, int Cin, int Hout, i
     p.conv_fast_b = stride == 1 && !ups && Hout == Hin && Wout == Win && Win > 1 && Hin > 1 && (long)p.K * Win < (1L << 32) && (long)p.K * Hin < (1L << 32);
     p.magic_w = (unsigned)((1UL << 32) / (unsigned long)Win) + 1u;
     p.magic_h = (unsigned)((1UL << 32) / (unsigned long)Hin) + 1u;
-    carve_tickets(p, workspace, workspace_bytes);
+    // Option CONVWG_STRIP (default 1): the shapes az_gemm_strip.inc covers stage one halo strip of X for all nine taps; 0, a forced
+    // tile and every other shape: the gather below, unchanged.  (The strip form leaves the finish to the separate launches.)
+    p.strip = (az_opt(AZ_OPT_CONVWG_STRIP) != 0 && !g_force_bm && strip_applies(p, workspace)) ? 1 : 0;
+    if (!p.strip) carve_tickets(p, workspace, workspace_bytes);
     if (bias_grad || seg_grad) {
       const int nseg = seg_grad ? batch : 1;
       int rc0 = carve_colsum(p, workspace, workspace_bytes, nseg, seg_grad ? Hout * Wout : p.K);
@@ -1578,7 +1586,7 @@ static int conv_impl(int mode, int batch, int Hin, int Win, int Cin, int Hout, i
     choose_split(p, split_k, workspace_bytes, true);
     if ((long)p.tiles_m * p.tiles_n > TICKET_BYTES / 4 || (long)p.ksplit * p.M * p.N * 4 >= 0x7FFFFFF0L) p.tickets = nullptr;
     if (p.tickets) AZ_HIP(hipMemsetAsync(p.tickets, 0, (size_t)p.tiles_m * p.tiles_n * 4, st));
-    rc = launch<A_COL, B_CONVWG>(p, st);
+    rc = p.strip ? launch_strip(p, st) : launch<A_COL, B_CONVWG>(p, st);
   } else {
     return AZ_ERR_ARG(18);
   }

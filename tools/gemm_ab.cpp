@@ -1,7 +1,9 @@
 // In-process A/B of GEMM / conv products between one or two builds of libaozora_hip.so (cdna_hip_programming.md 5.4 rule 24:
 // interleaved rounds in ONE process), through the C ABI with no Python between launches.
 //   build:  hipcc -O2 --offload-arch=gfx950 -o tools/gemm_ab tools/gemm_ab.cpp -ldl
-//   run:    tools/gemm_ab <libA.so> [<libB.so>] -- <case> [<case> ...]
+//   run:    tools/gemm_ab <libA.so>[@NAME=V] [<libB.so>[@NAME=V] ...] -- <case> [<case> ...]
+//           (one build, an option toggled: copies of the library under different names, e.g. a.so@CONVWG_STRIP=0 b.so@CONVWG_STRIP=0 c.so@CONVWG_STRIP=1
+//            -- the two equal sides are the measurement's own spread)
 //   case:   nt:M:N:K[:split]         C[M,N] = A[M,K] . W[N,K]^T             (az_gemm_bf16 0,1)
 //           tn:M:N:K[:split[:b]]     dW[M,N] = dY[K,M]^T . X[K,N] (+bias grad with :b)
 //           gg:M:H:K                 fused GEGLU forward: proj[M,2H] = X[M,K] . W[2H,K]^T + b, out[M,H] = value * gelu(gate)
@@ -68,7 +70,15 @@ struct Case { std::string kind; long v[8]; int nv; };
 int main(int argc, char** argv) {
   setvbuf(stdout, nullptr, _IOLBF, 0);
   std::vector<Lib> libs; int i = 1;
-  for (; i < argc && strcmp(argv[i], "--"); ++i) libs.push_back(load(argv[i]));
+  for (; i < argc && strcmp(argv[i], "--"); ++i) {      // lib.so[@NAME=V]: an option of that library alone (its own option table: give each side its own copy of the file)
+    std::string spec = argv[i]; const size_t at = spec.find('@');
+    libs.push_back(load(spec.substr(0, at).c_str()));
+    libs.back().name = spec;
+    if (at != std::string::npos) {
+      const std::string kv = spec.substr(at + 1); const size_t eq = kv.find('=');
+      if (eq == std::string::npos || libs.back().setopt(kv.substr(0, eq).c_str(), atoi(kv.c_str() + eq + 1))) { fprintf(stderr, "bad option %s\n", spec.c_str()); return 2; }
+    }
+  }
   if (libs.empty() || i >= argc) { fprintf(stderr, "usage: gemm_ab libA.so [libB.so] -- cases...\n"); return 2; }
   const long WS = 512L << 20;
   std::vector<void*> wss;
