@@ -124,13 +124,13 @@ class TrainStep:
         self._buckets: Dict[tuple, _Bucket] = {}
         self.last_pred_nhwc = None
         self.last_bucket = None
-        unet._arena_clients.add(self)
+        unet.acts.add_client(self)
 
     def _arena_replaced(self, arena):
         """AozoraUNet replaces an activation arena (a bucket needed more than it held; the device is synchronised): let go of
         every launch tape, graph and view made of its addresses before the old arena is released."""
         for bk in self._buckets.values():
-            if self.unet._arena_of(bk.parity) is arena:
+            if self.unet.acts.arena_of(bk.parity) is arena:
                 bk.discard_recorded()
         self.last_pred_nhwc = None
 
@@ -328,10 +328,9 @@ class TrainStep:
         key = (B, C, H, W, L, parity)
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
-            u.wait_pool_free(parity)            # deferred weight-gradient work of the previous user of this arena (any bucket of this parity)
-            gen = u.prepare_pool(parity)        # the previous micro-step found the arena too small: replaced here, between steps
-            u._defer_join = bool(defer_join)
-            u._pool_parity = parity
+            # the deferred weight-gradient work of the previous user of this arena (any bucket of this parity) is waited for, and an
+            # arena that user found too small is replaced here, between steps
+            gen = u.enter_micro_step(parity, defer_join)
             if key not in self._buckets:
                 bk = _Bucket(u.device, B, C, H, W, L, u.cfg.cross_attention_dim, u.cfg.pooled_dim,
                              (5 if self.loss_spec.needs_c else 4) + int(self.lora_dropout))

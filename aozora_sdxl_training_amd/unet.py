@@ -6,7 +6,8 @@ Design:
     `self.params` (params.ParamStore: layout, regions, W^T freshness, state dicts); the UNet binds the
     same buffers and dicts under its own names and forwards the store's methods;
   * activations are NHWC == row-major [B*H*W][C] bf16, so ResnetBlock2D and Transformer2DModel share
-    a layout and no permutes exist;
+    a layout and no permutes exist; their pools, arenas and gradient-buffer rules are `self.acts`
+    (activations.ActivationStore), shown under the UNet's old names in the same way;
   * forward records a tape of backward closures (static topology => the launch sequence is identical
     every step and can be captured into a hipGraph); all activations needed by the backward are kept
     (no gradient checkpointing: 288 GB HBM, SURVEY.md 8a row a8);
@@ -16,7 +17,6 @@ from __future__ import annotations
 
 import ctypes
 import math
-import weakref
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
@@ -29,6 +29,7 @@ from ._lib import lib, AozoraError, ForkEvent, Record, Wait, Live
 from .unet_spec import UNetConfig, SDXL_BASE, param_table, up_resnet_channels, LoraSpec, lora_table
 from .lora_exec import LoraAdapters
 from .params import ParamStore
+from .activations import Act, POOL_ALIGN, _Arena, _Pool, ActivationStore      # (the four names are re-exported: tests and tools import them from here)
 
 @dataclass
 class ExecPolicy:
@@ -66,114 +67,6 @@ BF16 = torch.bfloat16
 F32 = torch.float32
 
 
-class Act:
-    """An activation [rows][C] (2-D view, unit inner stride) and its gradient buffer."""
-    __slots__ = ("t", "g", "need_grad", "ready", "g_alias")
-
-    def __init__(self, t: torch.Tensor, need_grad: bool = True):
-        self.t = t
-        self.g: Optional[torch.Tensor] = None
-        self.need_grad = need_grad
-        self.ready = None     # event: g is being WRITTEN on the side stream (wait before READING g on main)
-        self.g_alias = False  # g IS some layer's dY (given by _give_grad): the parameter-gradient branch may read it at any later
-                              # time, so it is never written again -- the next contribution goes to a fresh buffer (g_new = g + ...)
-
-
-POOL_ALIGN = 256  # bytes: every pool buffer starts on a multiple of it inside the arena (the kernels need 16)
-
-
-class _Arena:
-    """ONE device allocation that all activation pools of a parity carve their buffers from.  Nothing in a pool lives across
-    micro-steps (every buffer is rewritten on every run), so the buckets of a run can share the memory of the largest one
-    instead of each holding its own.  A pool that needs more than the arena holds keeps the excess in buffers of its own for
-    that run and leaves the size it wants; grow() then REPLACES the arena by one of exactly that size -- the old one is
-    released first, so old and new never coexist -- and counts a generation: every address handed out before is dead."""
-
-    def __init__(self, device):
-        self.device = torch.device(device)
-        self.buf: Optional[torch.Tensor] = None
-        self.wanted = 0          # bytes the largest pool seen so far needs
-        self.generation = 0      # allocations so far; pools and launch tapes made under another value are stale
-
-    @property
-    def capacity(self) -> int:
-        return 0 if self.buf is None else self.buf.numel()
-
-    def want(self, nbytes: int):
-        self.wanted = max(self.wanted, int(nbytes))
-
-    def pending(self) -> bool:
-        return self.wanted > self.capacity
-
-    def view(self, off: int, nbytes: int, shape, dtype):
-        return self.buf[off:off + nbytes].view(dtype).view(shape)
-
-    def grow(self):
-        """The caller has synchronised the device and dropped every view of the old arena."""
-        self.buf = None
-        if self.device.type == "cuda":
-            torch.cuda.empty_cache()     # back to the driver before the new one is taken: the peak is not old + new
-        self.buf = torch.empty(self.wanted, dtype=torch.uint8, device=self.device)
-        self.generation += 1
-
-
-class _Pool:
-    """Static buffer pool: the n-th allocation of a step always returns the same tensor, so the
-    launch sequence (including addresses) repeats exactly and can be replayed from a hipGraph.
-    The buffers are views of the shared arena at bump-assigned offsets (allocation order, POOL_ALIGN-aligned); whatever
-    does not fit the arena as it stands is a tensor of its own until the arena has grown (_Arena)."""
-
-    def __init__(self, device, arena: Optional[_Arena] = None):
-        self.device = device
-        self.arena = arena if arena is not None else _Arena(device)
-        self.bufs: List[torch.Tensor] = []
-        self.offsets: List[int] = []
-        self.top = 0             # bytes assigned so far == offset of the next buffer
-        self.cursor = 0
-        self._gen = self.arena.generation
-        self._need, self._count = 0, 0     # need and buffer count of the last table that was dropped
-
-    def drop(self):
-        """Forget the offset table and every view (the arena was replaced): the next run assigns them again."""
-        if self.bufs:
-            self._need, self._count = self.top, len(self.bufs)
-        self.bufs, self.offsets, self.top, self.cursor = [], [], 0, 0
-        self._gen = self.arena.generation
-
-    def reset(self):
-        if self._gen != self.arena.generation:
-            self.drop()
-        self.cursor = 0
-
-    def get(self, shape, dtype=BF16):
-        if self.cursor < len(self.bufs):
-            t = self.bufs[self.cursor]
-            if tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-                raise AozoraError("activation pool replay mismatch (topology changed between steps)")
-        else:
-            nb = math.prod(shape) * dtype.itemsize
-            off, a = self.top, self.arena
-            self.top = off + (nb + POOL_ALIGN - 1) // POOL_ALIGN * POOL_ALIGN
-            if nb > 0 and off + nb <= a.capacity:
-                t = a.view(off, nb, shape, dtype)
-            else:
-                t = torch.empty(shape, dtype=dtype, device=self.device)
-            if self.top > a.capacity:
-                a.want(self.top)
-            self.bufs.append(t)
-            self.offsets.append(off)
-        self.cursor += 1
-        return t
-
-    def nbytes(self):
-        """What this bucket needs of the arena: the sum of its buffers, each rounded up to POOL_ALIGN."""
-        return self.top if self.bufs else self._need
-
-    def count(self):
-        """Buffers of this bucket (of its last complete table while the offsets wait to be assigned again)."""
-        return len(self.bufs) if self.bufs else self._count
-
-
 class _UNetCall(torch.autograd.Function):
     """Autograd bridge for the reference's own loop body: `pred = unet(...).sample; loss = f(pred);
     (loss / GA).backward()` (train.py:2760-2765).  forward = HIP forward, backward = HIP backward seeded
@@ -185,7 +78,7 @@ class _UNetCall(torch.autograd.Function):
         B, C, H, W = sample.shape
         unet.check_latent_shape(H, W)
         unet.begin_step((B, H, W, ehs.shape[1], "call"))
-        x8 = unet._pool.get((B, H, W, 8), BF16)
+        x8 = unet.acts.pool.get((B, H, W, 8), BF16)
         ops.nchw_to_nhwc_pad(sample.contiguous(), x8, C)
         pred = unet.forward_nhwc(x8, t_f32, ehs, pooled, tids_f32)
         out = torch.empty(B, unet.cfg.out_channels, H, W, dtype=BF16, device=sample.device)
@@ -196,7 +89,7 @@ class _UNetCall(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         unet, (B, H, W) = ctx.unet, ctx.geom
-        d8 = unet._pool.get((B, H, W, 8), BF16)
+        d8 = unet.acts.pool.get((B, H, W, 8), BF16)
         g = grad_out.contiguous()
         if g.dtype not in (BF16, F32):
             g = g.float()
@@ -243,11 +136,9 @@ class AozoraUNet:
                                       dora=self.dora)
                          if lora is not None else None)
         self._step_B = 1              # samples of the current step (forward_nhwc): rows / B = the rows of one sample, for rank dropout
-        self._pools: Dict[tuple, _Pool] = {}
-        self._pool: Optional[_Pool] = None
-        self._arenas: Dict[int, _Arena] = {}     # parity -> the arena its pools share (survives _pools.clear())
-        self.generation = 0                      # arena allocations so far, all parities (activation_bytes)
-        self._arena_clients = weakref.WeakSet()  # TrainStep objects: they hold launch tapes / graphs / views made of arena addresses
+        # the activation store (activations.py): pools, arenas, deferred readers, gradient-buffer rules
+        A = self.acts = ActivationStore(self.device, on_replace=self._arena_replaced)
+        self._pools, self._arenas, self._arena_clients = A.pools, A.arenas, A.clients      # never rebound: the same objects under the old names
         self._tape: List = []
         self.conv_in = True   # train.py:2694 probes hasattr(unet, 'conv_in')
         self._anchor = torch.zeros((), device=self.device, requires_grad=True)
@@ -269,8 +160,7 @@ class AozoraUNet:
         self._hoisted: Dict[str, Act] = {}      # forward outputs computed ahead by grouped launches (name -> Act)
         self._group_tables = {}
         self._side = self._sides[0]
-        # scheduling state (see _end_join); the data-parallel overlap's parameter side is the store's (params.py)
-        self._deferred = {}
+        # scheduling state (see _end_join, enter_micro_step); the data-parallel overlap's parameter side is the store's (params.py)
         self._defer_join = False
         self._pool_parity = 0
         self._after_tail_hook = None
@@ -370,19 +260,20 @@ class AozoraUNet:
         for sd in self._sides:
             ev = torch.cuda.Event(); ev.record(sd); evs.append(ev)
         if self._defer_join:
-            self._deferred[self._pool_parity] = evs
+            self.acts.leave_readers(self._pool_parity, evs)
         else:
             for ev in evs:
                 main.wait_event(ev)
-            self._deferred.clear()     # the in-order side stream(s) are fully drained now
+            self.acts.clear_readers()     # the in-order side stream(s) are fully drained now
 
-    def wait_pool_free(self, parity):
-        """Before a micro-step writes into activation pool `parity`: the deferred weight-gradient work that still reads it."""
-        for ev in self._deferred.pop(parity, []):
-            torch.cuda.current_stream().wait_event(ev)
-
-    def has_deferred(self):
-        return bool(self._deferred)
+    def enter_micro_step(self, parity, defer_join=False) -> int:
+        """TrainStep, before a micro-step on activation pool `parity` issues anything: wait for the deferred weight-gradient work of the
+        pool's previous user, replace the arena if that user found it too small, and note how this micro-step's backward ends
+        (_end_join).  -> the arena's generation (ActivationStore.prepare)."""
+        self.acts.wait_free(parity)
+        gen = self.acts.prepare(parity)
+        self._defer_join, self._pool_parity = bool(defer_join), parity
+        return gen
 
     def set_lora_dropout_seed(self, seed: int):
         """The seed of the LoRA dropout masks (config.SEED: masks are a function of (seed, micro-step) and of nothing else).  It rides
@@ -391,7 +282,7 @@ class AozoraUNet:
             return
         torch.cuda.synchronize(self.device)
         self.adapters.seed = int(seed)
-        for ts in list(self._arena_clients):
+        for ts in list(self.acts.clients):
             for bk in ts._buckets.values():
                 bk.discard_recorded()
 
@@ -461,54 +352,10 @@ class AozoraUNet:
         return AozoraUNet._Side(self)
 
     # ------------------------------------------------------------------ tape helpers --------------
-    def _new(self, rows, C, need_grad=True, dtype=BF16) -> Act:
-        return Act(self._pool.get((rows, C), dtype), need_grad)
-
     def _wait_ready(self, a: Act):
         if a.ready is not None:
             self._st_wait(torch.cuda.current_stream(), a.ready)
             a.ready = None
-
-    def _gbuf(self, a: Act):
-        """-> (dst, add) for writing a contribution to a's gradient: add is None (dst is overwritten), dst itself (accumulate in
-        place) or another tensor (dst = add + contribution, out of place).  Out of place exactly when the current gradient
-        storage is some layer's dY (g_alias): that layer's weight-gradient product, queued on the parameter-gradient branch,
-        reads it at an unspecified later time, and never having to wait for it is what lets the branch lag and its forks be
-        batched (one event per block instead of one per layer: the event packets cost the data-gradient stream 5-10 us each,
-        ~5 ms per micro-step, tools/trace_gaps.py)."""
-        if a.g is None:
-            a.g = self._pool.get(tuple(a.t.shape), BF16)
-            a.g_alias = False
-            return a.g, None
-        if a.g_alias:
-            old = a.g
-            a.g = self._pool.get(tuple(a.t.shape), BF16)
-            a.g_alias = False
-            return a.g, old
-        return a.g, a.g
-
-    def _gbuf_single(self, a: Act, what: str):
-        """Gradient buffer of an activation that must have exactly one consumer (no accumulation form in the kernel)."""
-        dst, add = self._gbuf(a)
-        if add is not None:
-            raise AozoraError(what + " must have a single consumer")
-        return dst
-
-    def _give_grad(self, a: Act, dy: torch.Tensor, alias=True):
-        """a.g += dy, aliasing dy's storage when a has no gradient yet (dy is dead afterwards for the data-gradient chain).
-        alias=True: dy is a layer's dY that the parameter-gradient branch still reads (see _gbuf)."""
-        if not a.need_grad:
-            return
-        if a.g is None:
-            a.g = dy
-            a.g_alias = alias
-        elif a.g_alias:
-            old = a.g
-            a.g = self._pool.get(tuple(a.t.shape), BF16)
-            a.g_alias = False
-            ops.add_rows(old, dy, a.g)
-        else:
-            ops.add_rows(a.g, dy, a.g)
 
     # ---- the parameter-gradient branch: weight / bias gradient launches are queued and issued in batches ----------------------
     def _side_defer(self, fn):
@@ -560,7 +407,7 @@ class AozoraUNet:
         """Queue the parked linear weight gradients on the parameter-gradient branch: as ONE grouped launch (every product over its
         whole k-range on 128x128 tiles -- no fp32 slabs, no reduce launches, the tiles of all products fill the chip together) when
         they add up to a chip-filling grid, else one split-K product each as before.  dY / X stay valid until the step ends: the
-        activation pool never re-uses a buffer inside a step and a buffer that is some layer's dY is never written again (_gbuf)."""
+        activation pool never re-uses a buffer inside a step and a buffer that is some layer's dY is never written again (acts.gbuf)."""
         jobs, self._tn_jobs = self._tn_jobs, []
         if jobs:
             tiles = sum(((dy.shape[1] + 127) // 128) * ((xt.shape[1] + 127) // 128) for dy, xt, _, _ in jobs)
@@ -620,13 +467,13 @@ class AozoraUNet:
     def _adapter_fwd(self, lg, x: Act, y: Act, geom=None, geglu_out: Optional[Act] = None):
         """The adapter follows the base product: u is taken from the pool behind y.  -> (u, whether the adapter is trainable).
         The rows of one sample (rank dropout): rows / B -- the context length for the K / V of a cross-attention, H W for a convolution."""
-        u = self._new(x.t.shape[0], lg.n * lg.r, need_grad=False)
+        u = self.acts.new(x.t.shape[0], lg.n * lg.r, need_grad=False)
         self.adapters.fwd(lg, x.t, u.t, y.t, geom, geglu_out.t if geglu_out is not None else None, x.t.shape[0] // self._step_B)
         return u, self.adapters.trainable(lg)
 
     def _adapter_du_buf(self, lg, x: Act) -> Optional[Act]:
         """du, first thing in a bwd(): whether or not the adapter is trainable (the pool's allocation order may not depend on the freeze mask)."""
-        return self._new(x.t.shape[0], lg.n * lg.r, need_grad=False) if lg is not None else None
+        return self.acts.new(x.t.shape[0], lg.n * lg.r, need_grad=False) if lg is not None else None
 
     def _adapter_bwd(self, lg, l_train, x: Act, u: Act, dy, du: Act, geom=None):
         """Behind the base layer's weight gradient, in front of its data gradient: du on the chain if the input has a gradient, and the
@@ -671,8 +518,8 @@ class AozoraUNet:
         if dora:
             # DoRA (INTEGRATION.md "DoRA"): v = the base product WITHOUT bias and residual (a hoisted one: `pre`), the up product on v in
             # place, then y = g v + bias + residual; v is kept for the backward.  The GEGLU follows on y: no fused form.
-            v = pre if pre is not None else self._new(rows, N, need_grad=False)
-            y = out if out is not None else self._new(rows, N)
+            v = pre if pre is not None else self.acts.new(rows, N, need_grad=False)
+            y = out if out is not None else self.acts.new(rows, N)
             if pre is None:
                 ops.gemm(x.t, W, v.t, trans_b=True, split_k=0 if (rows <= 512 and residual is None) else 1)
             u, l_train = self._adapter_fwd(lg, x, v)
@@ -682,7 +529,7 @@ class AozoraUNet:
         elif pre is not None:
             y = pre
         else:
-            y = out if out is not None else self._new(rows, N)
+            y = out if out is not None else self.acts.new(rows, N)
             if geglu_out is not None and lg is None:
                 ops.gemm_geglu_fwd(x.t, W, self._w[bname] if bname else None, y.t, geglu_out.t)
             else:
@@ -700,7 +547,7 @@ class AozoraUNet:
                 return
             du = self._adapter_du_buf(lg, x)
             # DoRA: every consumer of dy but the bias and the residual reads dv = g dy (pool order independent of the freeze mask)
-            dyv = self._pool.get(tuple(dy.shape), BF16) if dora else dy
+            dyv = self.acts.pool.get(tuple(dy.shape), BF16) if dora else dy
             on_side = side_dgrad and self.policy.temb_side and self.concurrent_wgrad and len(self._sides) == 1
             if dora and on_side:      # dy would be produced on the branch and read by az_dora_bwd_bf16 on the chain, unordered
                 raise AozoraError("DoRA on a layer whose data gradient runs on the parameter-gradient branch (side_dgrad) is not supported")
@@ -740,7 +587,7 @@ class AozoraUNet:
             if lg is not None:
                 self._adapter_bwd(lg, l_train, x, u, dyv, du)
             if x.need_grad:
-                dx, add = self._gbuf(x)
+                dx, add = self.acts.gbuf(x)
                 oop = add is not None and add is not dx
 
                 def dgrad():
@@ -753,8 +600,8 @@ class AozoraUNet:
                     x.ready = self._flush_side()
                 else:
                     dgrad()
-            if residual is not None:   # dy becomes the residual's gradient (never written again: _gbuf)
-                self._give_grad(residual, dy)
+            if residual is not None:   # dy becomes the residual's gradient (never written again: acts.gbuf)
+                self.acts.give_grad(residual, dy)
         self._tape.append(bwd)
         return y
 
@@ -780,7 +627,7 @@ class AozoraUNet:
         Cout, ks, _, Cin = Wt.shape
         Ho = (H + 2 - 3) // stride + 1
         Wo = (W_ + 2 - 3) // stride + 1
-        y = out if out is not None else self._new(B * Ho * Wo, Cout)      # out: a [rows][Cout] view with any row stride (one half of a skip concat)
+        y = out if out is not None else self.acts.new(B * Ho * Wo, Cout)      # out: a [rows][Cout] view with any row stride (one half of a skip concat)
         if tuple(y.t.shape) != (B * Ho * Wo, Cout):
             raise AozoraError("conv destination shape")
         x4 = ops.as4(x.t, B, Hs, Ws)
@@ -803,7 +650,7 @@ class AozoraUNet:
             dy4 = ops.as4(dy, B, Ho, Wo)
             need_seg = rowbias is not None and rowbias.need_grad
             if need_seg:
-                self._gbuf_single(rowbias, "segment-sum target")      # allocate on the main path (pool order is stream-agnostic)
+                self.acts.gbuf_single(rowbias, "segment-sum target")      # allocate on the main path (pool order is stream-agnostic)
             self._wait_ready(y)
 
             def wgrad():
@@ -824,12 +671,12 @@ class AozoraUNet:
             if lg is not None:
                 self._adapter_bwd(lg, l_train, x, u, dy, du, geom)
             if x.need_grad:
-                dx, add = self._gbuf(x)
+                dx, add = self.acts.gbuf(x)
                 if upsample:            # d(upsampled x) into a scratch buffer, then the 2x2 -> 1 fold into dx
                     if add is not None:
                         raise AozoraError("upsample input must have a single consumer")
                     dxs = dx
-                    dx = self._pool.get((B * H * W_, Cin), BF16)
+                    dx = self.acts.pool.get((B * H * W_, Cin), BF16)
                 oop = add is not None and add is not dx
                 res4 = ops.as4(add, B, H, W_) if oop else None
                 if Cout % 8 == 0 and dy.shape[1] == Cout:
@@ -845,7 +692,7 @@ class AozoraUNet:
                 elif upsample:
                     ops.upsample2x_bwd(dx.view(B, H, W_, Cin), dxs.view(B, Hs, Ws, Cin))
             if residual is not None:
-                self._give_grad(residual, dy)
+                self.acts.give_grad(residual, dy)
         self._tape.append(bwd)
         return y, (B, Ho, Wo)
 
@@ -853,8 +700,8 @@ class AozoraUNet:
         B, H, W_ = geom
         C = x.t.shape[1]
         G = self.cfg.norm_groups
-        y = self._new(B * H * W_, C)
-        stats = self._pool.get((B * G * 2,), F32)
+        y = self.acts.new(B * H * W_, C)
+        stats = self.acts.pool.get((B * G * 2,), F32)
         gam, bet = self._w[prefix + ".weight"], self._w[prefix + ".bias"]
         x3 = ops.as3(x.t, B, H * W_)
         ops.groupnorm_fwd(x3, gam, bet, y.t.view(B, H * W_, C), stats, G, eps, silu)
@@ -867,7 +714,7 @@ class AozoraUNet:
             dy3 = ops.as3(dy, B, H * W_)
             dx3, add3 = None, None
             if x.need_grad:
-                dx, add = self._gbuf(x)
+                dx, add = self.acts.gbuf(x)
                 dx3 = ops.as3(dx, B, H * W_)
                 if add is not None:
                     add3 = ops.as3(add, B, H * W_)
@@ -878,8 +725,8 @@ class AozoraUNet:
 
     def layernorm(self, x: Act, prefix) -> Act:
         rows, C = x.t.shape
-        y = self._new(rows, C)
-        stats = self._pool.get((2 * rows,), F32)
+        y = self.acts.new(rows, C)
+        stats = self.acts.pool.get((2 * rows,), F32)
         gam, bet = self._w[prefix + ".weight"], self._w[prefix + ".bias"]
         ops.layernorm_fwd(x.t, gam, bet, y.t, stats, 1e-5)
 
@@ -887,7 +734,7 @@ class AozoraUNet:
             dy = y.g
             if dy is None:
                 return
-            dx, add = self._gbuf(x)
+            dx, add = self.acts.gbuf(x)
             gw = self._gw[prefix + ".weight"] if self._trainable(prefix + ".weight") else None
             gb = self._gw[prefix + ".bias"] if self._trainable(prefix + ".bias") else None
             self._wait_ready(y)
@@ -898,7 +745,7 @@ class AozoraUNet:
                     # (The buffer is taken whether or not the parameters are frozen: the pool's allocation order may not
                     # depend on the freeze mask.)
                     nblk = ops.ln_partial_blocks(rows)
-                    part = self._pool.get((nblk * C * 2,), F32)
+                    part = self.acts.pool.get((nblk * C * 2,), F32)
                 if self.policy.ln_defer and (gw is not None or gb is not None):
                     ops.layernorm_bwd_partial(x.t, gam, stats, dy, dx, part, dx_add=add, nblk=nblk)
                     self._ln_jobs.append((part, gw, gb, nblk, C))
@@ -912,14 +759,14 @@ class AozoraUNet:
         return y
 
     def silu(self, x: Act) -> Act:
-        y = self._new(*x.t.shape)
+        y = self.acts.new(*x.t.shape)
         ops.silu_fwd(x.t, y.t)
 
         def bwd():
             if y.g is None:
                 return
             self._wait_ready(y)
-            dx, add = self._gbuf(x)
+            dx, add = self.acts.gbuf(x)
             if add is not None and add is not dx:
                 raise AozoraError("SiLU input gradient cannot be accumulated out of place")
             ops.silu_bwd(x.t, y.g, dx, accumulate=add is dx)
@@ -947,22 +794,22 @@ class AozoraUNet:
             k3 = kv.t.view(B, ctx_len, 2 * C)[..., :C]
             v3 = kv.t.view(B, ctx_len, 2 * C)[..., C:]
             Tk = ctx_len
-        o = self._new(B * T, C)
-        lse = self._pool.get((B * heads * T,), F32)
+        o = self.acts.new(B * T, C)
+        lse = self.acts.pool.get((B * heads * T,), F32)
         ops.attn_fwd(q3, k3, v3, o.t.view(B, T, C), lse, heads, scale)
 
         def bwd():
             do = o.g
             if do is None:
                 return
-            delta = self._pool.get((B * heads * T,), F32)
+            delta = self.acts.pool.get((B * heads * T,), F32)
             if ctx is None:
-                dqkv = self._gbuf_single(qkv, "attention projections")
+                dqkv = self.acts.gbuf_single(qkv, "attention projections")
                 d3 = dqkv.view(B, T, 3 * C)
                 dq3, dk3, dv3 = d3[..., :C], d3[..., C:2 * C], d3[..., 2 * C:]
             else:
-                dq = self._gbuf_single(q, "attention projections")
-                dkv = self._gbuf_single(kv, "attention projections")
+                dq = self.acts.gbuf_single(q, "attention projections")
+                dkv = self.acts.gbuf_single(kv, "attention projections")
                 dq3 = dq.view(B, T, C)
                 dk3, dv3 = dkv.view(B, ctx_len, 2 * C)[..., :C], dkv.view(B, ctx_len, 2 * C)[..., C:]
             o3, do3 = o.t.view(B, T, C), do.view(B, T, C)
@@ -985,13 +832,13 @@ class AozoraUNet:
         if pre is not None:
             y = pre
         else:
-            y = self._new(rows, H2 // 2)
+            y = self.acts.new(rows, H2 // 2)
             ops.geglu_fwd(proj.t, y.t)
 
         def bwd():
             if y.g is None:
                 return
-            dp = self._gbuf_single(proj, "GEGLU projection")
+            dp = self.acts.gbuf_single(proj, "GEGLU projection")
             ops.geglu_bwd(proj.t, y.g, dp)
         self._tape.append(bwd)
         return y
@@ -1015,7 +862,7 @@ class AozoraUNet:
             if not jobs:
                 continue
             rows, K = a.t.shape
-            outs = [self._new(rows, W.shape[0]) for _, W, _ in jobs]
+            outs = [self.acts.new(rows, W.shape[0]) for _, W, _ in jobs]
             key = (a.t.data_ptr(), rows, K) + tuple((W.data_ptr(), o.t.data_ptr(), b.data_ptr() if b is not None else 0, W.shape[0], W.stride(0),
                                                       o.t.stride(0)) for (_, W, b), o in zip(jobs, outs))
             tab = self._group_tables.get(key)
@@ -1066,8 +913,8 @@ class AozoraUNet:
         n = self.layernorm(h, pre + ".norm3")
         if self.policy.geglu_fuse:       # the GEGLU rides in the epilogue of its projection (pool order: projection first, output second, as unfused)
             W0 = self._w[pre + ".ff.net.0.proj.weight"]
-            p_out = self._new(n.t.shape[0], W0.shape[0])
-            g_out = self._new(n.t.shape[0], W0.shape[0] // 2)
+            p_out = self.acts.new(n.t.shape[0], W0.shape[0])
+            g_out = self.acts.new(n.t.shape[0], W0.shape[0] // 2)
             p = self.linear(n, pre + ".ff.net.0.proj.weight", pre + ".ff.net.0.proj.bias", out=p_out, geglu_out=g_out)
             g = self.geglu(p, pre=g_out)
         else:
@@ -1116,15 +963,15 @@ class AozoraUNet:
                     or a.t.stride(0) != ld or b.t.stride(0) != ld):
                 raise AozoraError("in-place concat: the halves are not views of the destination")
         else:
-            y = self._new(rows, C1 + C2)
+            y = self.acts.new(rows, C1 + C2)
             ops.add_rows(a.t, None, y.t[:, :C1])
             ops.add_rows(b.t, None, y.t[:, C1:])
 
         def bwd():
             if y.g is None:
                 return
-            self._give_grad(a, y.g[:, :C1], alias=y.g_alias)      # slices of the concat's gradient (nobody's dY unless y.g is)
-            self._give_grad(b, y.g[:, C1:], alias=y.g_alias)
+            self.acts.give_grad(a, y.g[:, :C1], alias=y.g_alias)      # slices of the concat's gradient (nobody's dY unless y.g is)
+            self.acts.give_grad(b, y.g[:, C1:], alias=y.g_alias)
         self._tape.append(bwd)
         return y
 
@@ -1133,13 +980,13 @@ class AozoraUNet:
         B, H, W_ = geom
         C = x.t.shape[1]
         Ho, Wo = up_to if up_to is not None else (2 * H, 2 * W_)
-        y = self._new(B * Ho * Wo, C)
+        y = self.acts.new(B * Ho * Wo, C)
         ops.upsample_nearest_fwd(x.t.view(B, H, W_, C), y.t.view(B, Ho, Wo, C))
 
         def bwd():
             if y.g is None:
                 return
-            dx = self._gbuf_single(x, "upsample input")
+            dx = self.acts.gbuf_single(x, "upsample input")
             if not y.g.is_contiguous():
                 raise AozoraError("upsample gradient must be contiguous")
             ops.upsample_nearest_bwd(y.g.view(B, Ho, Wo, C), dx.view(B, H, W_, C))
@@ -1158,55 +1005,27 @@ class AozoraUNet:
         except Exception:
             pass
 
-    # ------------------------------------------------------------------ activation arena ---------
-    def _arena_of(self, parity) -> _Arena:
-        """The arena of a pool key's last component: 0 / 1 (TrainStep, two under double_buffer); everything else -- the "call" key
-        of the autograd bridge among them -- shares parity 0's."""
-        k = parity if parity in (0, 1) else 0
-        if k not in self._arenas:
-            self._arenas[k] = _Arena(self.device)
-        return self._arenas[k]
+    # ------------------------------------------------------------------ activations --------------
+    # The activation store (activations.py) under the names callers use; the layers call self.acts directly.
+    _pool = property(lambda self: self.acts.pool)                # rebound during a run: read through, never held
+    generation = property(lambda self: self.acts.generation)
+    def activation_bytes(self) -> dict: return self.acts.activation_bytes()
+    def prepare_pool(self, parity) -> int: return self.acts.prepare(parity)
+    def wait_pool_free(self, parity): return self.acts.wait_free(parity)
+    def has_deferred(self): return self.acts.has_deferred()
+    def _arena_of(self, parity) -> _Arena: return self.acts.arena_of(parity)
+    def _settle_arena(self, arena: _Arena): return self.acts.settle(arena)
 
-    def _settle_arena(self, arena: _Arena):
-        """Between micro-steps: if some pool of `arena` wanted more than it holds, replace it.  Order matters -- the device is
-        synchronised first (deferred weight-gradient work, a launched hipGraph and the C-side tape player may still use the old
-        addresses), then every holder of those addresses lets go (pools, parked jobs, the launch tapes / graphs of the
-        TrainStep objects), then the old arena goes back to the driver, then the new one is taken."""
-        if not arena.pending():
-            return
-        torch.cuda.synchronize(self.device)
-        self._deferred.clear()
-        for pool in self._pools.values():
-            if pool.arena is arena:
-                pool.drop()
-        self._pool = None
+    def _arena_replaced(self, arena: _Arena):
+        """The store replaces `arena` (ActivationStore.settle: the device is synchronised, the arena's pools are dropped, the old
+        memory is still held): the executor's own holders of its addresses let go -- the per-step lists, then the launch tapes /
+        graphs of the TrainStep objects."""
         self._tape, self._side_q, self._ln_jobs, self._tn_jobs, self._xkv_jobs, self._hoisted = [], [], [], [], [], {}
         # the pointer tables (_ln_tables, _tn_tables, _group_tables) stay: recorded launches of the OTHER parity's buckets hold their
         # raw addresses, and their keys carry everything a record holds, so an entry made of dead addresses can only be found
         # again by a launch that means exactly those addresses and shapes
-        for client in list(self._arena_clients):
+        for client in list(self.acts.clients):
             client._arena_replaced(arena)
-        arena.grow()
-        self.generation += 1
-
-    def prepare_pool(self, parity) -> int:
-        """Called by TrainStep before a micro-step on `parity` issues anything: grows the arena if the previous micro-step asked
-        for it.  -> the arena's generation; whatever recorded addresses under another value must be rebuilt."""
-        arena = self._arena_of(parity)
-        self._settle_arena(arena)
-        return arena.generation
-
-    def activation_bytes(self) -> dict:
-        """{"arena": {parity: bytes held}, "need": {pool key: bytes that bucket needs}, "generation": arena allocations so far}.
-        All buckets of a parity share one arena, sized for the largest of them: after any sequence of buckets
-        arena <= max need + 256 B x (buffers of that bucket).  An arena that is too small is replaced, which counts a generation
-        and makes every bucket of that parity rebuild its launch tape / graph on its next visit.
-        Because the buckets overwrite each other's activations, `TrainStep.last_pred_nhwc`, `bk.pred` and `bk.per_sample` of a
-        bucket are valid until the next micro-step of ANY bucket of the same parity (not, as with one pool per bucket, until the
-        next visit of the same bucket): read them before that."""
-        return {"arena": {k: a.capacity for k, a in self._arenas.items()},
-                "need": {k: p.nbytes() for k, p in self._pools.items()},
-                "generation": self.generation}
 
     def check_latent_shape(self, H: int, W: int):
         """Every latent size whose sides hold one pixel per level of the coarsest grid runs (SDXL: H, W >= 4); a side that is no
@@ -1222,14 +1041,8 @@ class AozoraUNet:
         lib()._fn["az_make_current"](self._ctx)      # this thread's launches read THIS UNet's option table from here on
         if self.adapters is not None:
             self.adapters.step_word = lora_step_word
-        arena = self._arena_of(key[-1])
-        if lib().recorder is None:
-            self._settle_arena(arena)
-        if key not in self._pools:
-            self._pools[key] = _Pool(self.device, arena)
+        self.acts.begin(key, recording=lib().recorder is not None)
         self.refresh_transposed()
-        self._pool = self._pools[key]
-        self._pool.reset()
         self._tape = []
         self._ev_cursor = 0
         self._side_used = False
@@ -1257,14 +1070,14 @@ class AozoraUNet:
         # around: measured 0.851 vs 0.835 it/s)
         self._live(lib().call, "az_gemm_set_exclusive", 1)
         # ---- embeddings (a7.1) ----
-        tsin = self._new(B, ch[0], need_grad=False)
+        tsin = self.acts.new(B, ch[0], need_grad=False)
         ops.timestep_embed(t_f32, ch[0], tsin.t)
         e = self.linear(tsin, "time_embedding.linear_1.weight", "time_embedding.linear_1.bias")
         e = self.silu(e)
         emb_t = self.linear(e, "time_embedding.linear_2.weight", "time_embedding.linear_2.bias")
-        idsin = self._new(B * 6, cfg.addition_time_embed_dim, need_grad=False)
+        idsin = self.acts.new(B * 6, cfg.addition_time_embed_dim, need_grad=False)
         ops.timestep_embed(time_ids_f32.reshape(-1), cfg.addition_time_embed_dim, idsin.t)
-        addin = self._new(B, cfg.add_in_dim, need_grad=False)
+        addin = self.acts.new(B, cfg.add_in_dim, need_grad=False)
         ops.add_rows(pooled, None, addin.t[:, :cfg.pooled_dim])
         ops.add_rows(idsin.t.view(B, 6 * cfg.addition_time_embed_dim), None, addin.t[:, cfg.pooled_dim:])
         a = self.linear(addin, "add_embedding.linear_1.weight", "add_embedding.linear_1.bias")
@@ -1292,7 +1105,7 @@ class AozoraUNet:
             if not self.policy.cat_inplace:
                 return None
             u = n_skips - 1 - len(skips)
-            cat = self._new(rows, c1_of(u) + C2)
+            cat = self.acts.new(rows, c1_of(u) + C2)
             cats[u] = cat
             return Act(cat.t[:, c1_of(u):])
 

@@ -1,12 +1,13 @@
-"""The activation arena and its pools (unet._Arena / unet._Pool) are pure bookkeeping and run on the CPU: offsets, replay,
-growth, generations and the memory bound  arena <= max need + 256 B x (buffers of the largest bucket)."""
+"""The activation arena, its pools and the store that replaces arenas (activations._Arena / _Pool / ActivationStore) are pure
+bookkeeping and run on the CPU: offsets, replay, growth, generations and the memory bound
+arena <= max need + 256 B x (buffers of the largest bucket)."""
 import itertools
 
 import pytest
 import torch
 
 from aozora_sdxl_training_amd._lib import AozoraError
-from aozora_sdxl_training_amd.unet import POOL_ALIGN, _Arena, _Pool
+from aozora_sdxl_training_amd.activations import POOL_ALIGN, ActivationStore, _Arena, _Pool
 
 BF16, F32 = torch.bfloat16, torch.float32
 SMALL = [((3, 5), BF16), ((7,), F32), ((2, 4, 4, 8), BF16), ((129,), BF16), ((64, 2), F32)]
@@ -29,7 +30,7 @@ def _need(shapes):
 
 
 def _settle(arena):
-    """What AozoraUNet._settle_arena does between micro-steps, without the device."""
+    """What ActivationStore.settle does to the arena between micro-steps, without the device."""
     if arena.pending():
         arena.grow()
         return True
@@ -182,17 +183,18 @@ def test_arena_is_bounded_by_the_largest_bucket(order):
 
 
 def test_replacing_an_arena_keeps_what_other_parities_recorded(monkeypatch):
-    """AozoraUNet._settle_arena on a bare object (no device): the device is synchronised BEFORE anything is released, the
-    TrainStep objects let go before the old arena does, only pools of the replaced arena are dropped -- and the pointer tables
-    stay: launch tapes of the other parity hold their raw addresses (they were once cleared here, and a double-buffered run
-    replayed a tape over freed tables)."""
+    """ActivationStore.settle with no device, its on_replace the executor's own hook (AozoraUNet._arena_replaced on a bare object
+    that has only the fields the hook touches): the device is synchronised BEFORE anything is released, the TrainStep objects let
+    go before the old arena does, only pools of the replaced arena are dropped -- and the pointer tables stay: launch tapes of the
+    other parity hold their raw addresses (they were once cleared here, and a double-buffered run replayed a tape over freed
+    tables)."""
     from aozora_sdxl_training_amd.unet import AozoraUNet
     log = []
     monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: log.append("sync"))
     u = object.__new__(AozoraUNet)
-    u.device = torch.device("cpu")
-    u._arenas, u._pools, u._pool, u.generation = {}, {}, None, 0
-    u._deferred = {0: ["ev"]}
+    s = u.acts = ActivationStore("cpu", on_replace=u._arena_replaced)
+    assert (s.pools, s.pool, s.arenas, s.generation, s.deferred) == ({}, None, {}, 0, {})
+    s.leave_readers(0, ["ev"])
     u._tape, u._side_q, u._ln_jobs, u._tn_jobs, u._xkv_jobs, u._hoisted = [1], [1], [1], [1], [1], {"a": 1}
     table = torch.zeros(4, dtype=torch.int64)
     u._ln_tables, u._tn_tables, u._group_tables = {"k": table}, {"k": table}, {"k": table}
@@ -201,25 +203,45 @@ def test_replacing_an_arena_keeps_what_other_parities_recorded(monkeypatch):
         def _arena_replaced(self, arena):
             log.append(("client", arena.capacity))
     client = Client()
-    u._arena_clients = {client}
-    a0, a1 = u._arena_of(0), u._arena_of(1)
-    assert u._arena_of("call") is a0 and a0 is not a1
+    s.add_client(client)
+    a0, a1 = s.arena_of(0), s.arena_of(1)
+    assert s.arena_of("call") is a0 and a0 is not a1
     for key, arena, shapes in (((2, 16, 16, 77, 0), a0, SMALL), ((2, 16, 16, 77, 1), a1, MID)):
-        u._pools[key] = _Pool("cpu", arena)
-        _run(u._pools[key], shapes)
-    assert u.prepare_pool(0) == 1 and log == ["sync", ("client", 0)]
-    assert u.prepare_pool(1) == 1 and u.generation == 2
-    p0, p1 = u._pools[(2, 16, 16, 77, 0)], u._pools[(2, 16, 16, 77, 1)]
+        s.pools[key] = _Pool("cpu", arena)
+        _run(s.pools[key], shapes)
+    assert s.prepare(0) == 1 and log == ["sync", ("client", 0)]
+    assert not s.has_deferred()
+    assert (u._tape, u._side_q, u._ln_jobs, u._tn_jobs, u._xkv_jobs, u._hoisted) == ([], [], [], [], [], {})
+    assert s.prepare(1) == 1 and s.generation == 2
+    p0, p1 = s.pools[(2, 16, 16, 77, 0)], s.pools[(2, 16, 16, 77, 1)]
     _run(p0, SMALL); _run(p1, MID)
     addr1 = [b.data_ptr() for b in p1.bufs]
     # a larger bucket on parity 0
-    u._pools[(2, 24, 24, 77, 0)] = _Pool("cpu", a0)
-    _run(u._pools[(2, 24, 24, 77, 0)], LARGE)
+    s.pools[(2, 24, 24, 77, 0)] = _Pool("cpu", a0)
+    _run(s.pools[(2, 24, 24, 77, 0)], LARGE)
     del log[:]
-    assert u.prepare_pool(1) == 1 and log == []                      # nothing pending there
-    assert u.prepare_pool(0) == 2 and log == ["sync", ("client", _need(SMALL))]
-    assert u.generation == 3 and a0.capacity == _need(LARGE) and a1.generation == 1
+    assert s.prepare(1) == 1 and log == []                      # nothing pending there
+    assert s.prepare(0) == 2 and log == ["sync", ("client", _need(SMALL))]
+    assert s.generation == 3 and a0.capacity == _need(LARGE) and a1.generation == 1
     assert not p0.bufs and [b.data_ptr() for b in p1.bufs] == addr1   # parity 1 keeps its views
     assert u._ln_tables == {"k": table} and u._tn_tables == {"k": table} and u._group_tables == {"k": table}
-    assert u.activation_bytes() == {"arena": {0: _need(LARGE), 1: _need(MID)}, "generation": 3,
+    assert s.activation_bytes() == {"arena": {0: _need(LARGE), 1: _need(MID)}, "generation": 3,
                                     "need": {(2, 16, 16, 77, 0): _need(SMALL), (2, 16, 16, 77, 1): _need(MID), (2, 24, 24, 77, 0): _need(LARGE)}}
+    # ... and the UNet's forwarders and properties read the same store
+    assert u.activation_bytes() == s.activation_bytes() and u.generation == 3 and u._pool is s.pool and u._arena_of(1) is a1
+    assert u.prepare_pool(0) == 2 and not u.has_deferred()
+
+
+def test_begin_settles_makes_and_rewinds_the_pool_but_never_settles_under_a_recording(monkeypatch):
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    s = ActivationStore("cpu")
+    key = (2, 16, 16, 77, 1)
+    s.begin(key, recording=False)
+    assert s.pool is s.pools[key] and s.pool.arena is s.arena_of(1) and s.generation == 0
+    [s.pool.get(shape, dtype) for shape, dtype in SMALL]
+    s.begin(key, recording=True)                 # pending, but a recording is running: the arena stays as it is
+    assert s.generation == 0 and s.pool is s.pools[key] and s.pool.cursor == 0 and s.pool.bufs
+    s.begin(key, recording=False)
+    assert s.generation == 1 and s.arena_of(1).capacity == _need(SMALL) and s.pool is s.pools[key] and not s.pool.bufs
+    s.begin((2, 16, 16, 77, "call"), recording=False)
+    assert s.pool.arena is s.arena_of(0)

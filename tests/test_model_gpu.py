@@ -794,3 +794,31 @@ def test_the_parameter_store_is_the_only_holder_of_its_state(setup):
     for name in ("_wt_dirty", "_wt_version", "_wt_ready", "_region_events", "_wt_region_pending", "_grads_busy", "_wt_tables"):
         assert name not in unet.__dict__ and name in unet.params.__dict__, name
     assert not unet.params._wt_dirty and unet.params._wt_tables
+
+
+@pytest.mark.gpu
+def test_the_activation_store_is_the_only_holder_of_its_state(setup):
+    """AozoraUNet shows the pool and arena tables of its ActivationStore (activations.py) as the same objects and reads the current pool
+    and the generation through it: after a micro-step nothing of the store's mutable state lives on the UNet.  (A UNet of its own: the
+    generation counts what this one micro-step asked for.  The arena is taken BETWEEN micro-steps -- the first run of a bucket holds its
+    buffers itself -- so the count is read behind the prepare_pool the next micro-step would begin with.)"""
+    from aozora_sdxl_training_amd.train_step import TrainStep
+    from aozora_sdxl_training_amd.unet import AozoraUNet
+    pc, oc, params, _ = setup
+    unet = AozoraUNet(pc, DEV).load_state_dict(params)
+    lat, noise, ctx, pooled, tid, ts, jit = _inputs(1, 8, 8, pc)
+    step = TrainStep(unet, mode="epsilon", grad_accum=1, use_graph=False, double_buffer=True)
+    unet.zero_grad()
+    assert math.isfinite(step.micro_step(lat.to(DEV), noise.to(DEV), ts, ctx.to(DEV), pooled.to(DEV), tid.to(DEV), jit).item())
+    step.synchronize()
+    assert unet._pools is unet.acts.pools and unet._arenas is unet.acts.arenas and unet._arena_clients is unet.acts.clients
+    assert unet._pool is unet.acts.pool and unet._pool is unet._pools[(1, 8, 8, 77, 0)]
+    for name in ("pool", "generation", "deferred"):
+        assert name in unet.acts.__dict__ and name not in unet.__dict__, name
+    assert not {"_pool", "_deferred"} & set(unet.__dict__)
+    assert step in unet.acts.clients and not unet.has_deferred()
+    print("generation behind the micro-step", unet.generation, "arena", unet.activation_bytes()["arena"])
+    assert unet.prepare_pool(0) == 1
+    ab = unet.activation_bytes()
+    assert ab["generation"] == 1 and unet.generation == 1 and unet.acts.generation == 1
+    assert ab["arena"] == {0: ab["need"][(1, 8, 8, 77, 0)]}
