@@ -78,6 +78,34 @@ class Live(NamedTuple):         # host logic that depends on run-time state: fn(
     args: tuple
 
 
+# The stream / event operations and the state-dependent host logic of a launch sequence go through these three, so that a
+# recording (lib().recorder) captures them next to the ABI launches.
+def record_event(ev, stream):
+    ev.record(stream)
+    rec = lib().recorder
+    if rec is not None:
+        rec.append(Record(ev, stream))
+
+
+def wait_event(stream, ev):
+    ev.wait(stream)
+    rec = lib().recorder
+    if rec is not None:
+        rec.append(Wait(stream, ev))
+
+
+def run_live(fn, *args):
+    """Run fn(*args) now with recording suspended and put the call itself on the tape (state-dependent host logic)."""
+    L = lib()
+    rec, L.recorder = L.recorder, None
+    try:
+        fn(*args)
+    finally:
+        L.recorder = rec
+    if rec is not None:
+        rec.append(Live(fn, args))
+
+
 class _Lib:
     def __init__(self):
         if not os.path.exists(LIB_PATH):

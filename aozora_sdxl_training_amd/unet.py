@@ -8,6 +8,7 @@ Design:
   * activations are NHWC == row-major [B*H*W][C] bf16, so ResnetBlock2D and Transformer2DModel share
     a layout and no permutes exist; their pools, arenas and gradient-buffer rules are `self.acts`
     (activations.ActivationStore), shown under the UNet's old names in the same way;
+  * the weight / bias gradient launches of the backward go through `self.branch` (branch.GradBranch: queue, batches, parked work, forks, join);
   * forward records a tape of backward closures (static topology => the launch sequence is identical
     every step and can be captured into a hipGraph); all activations needed by the backward are kept
     (no gradient checkpointing: 288 GB HBM, SURVEY.md 8a row a8);
@@ -25,11 +26,12 @@ import os
 import torch
 
 from . import ops
-from ._lib import lib, AozoraError, ForkEvent, Record, Wait, Live
+from ._lib import lib, AozoraError, wait_event, run_live
 from .unet_spec import UNetConfig, SDXL_BASE, param_table, up_resnet_channels, LoraSpec, lora_table
 from .lora_exec import LoraAdapters
 from .params import ParamStore
 from .activations import Act, POOL_ALIGN, _Arena, _Pool, ActivationStore      # (the four names are re-exported: tests and tools import them from here)
+from .branch import GradBranch
 
 @dataclass
 class ExecPolicy:
@@ -142,31 +144,17 @@ class AozoraUNet:
         self._tape: List = []
         self.conv_in = True   # train.py:2694 probes hasattr(unet, 'conv_in')
         self._anchor = torch.zeros((), device=self.device, requires_grad=True)
-        # backward concurrency: each layer's wgrad (+ bias grad) runs on a forked stream beside its dgrad
-        self.concurrent_wgrad = True
-        # parameter-gradient branch streams (round-robin): independent weight-gradient products of moderate size run
-        # side by side instead of each being split-K'ed to fill the chip on its own (side_priority -1, a high-priority branch: +1 ms)
-        self._sides = [torch.cuda.Stream(device=self.device, priority=self.policy.side_priority)
-                       for _ in range(max(1, self.policy.side_streams))]
+        # the parameter-gradient branch (branch.py): the queue of weight / bias gradient launches, what the layers park, the fork events.
+        # Its streams (round-robin): independent weight-gradient products of moderate size run side by side instead of each being
+        # split-K'ed to fill the chip on its own (side_priority -1, a high-priority branch: +1 ms)
+        self.branch = GradBranch(self.policy, A, [torch.cuda.Stream(device=self.device, priority=self.policy.side_priority)
+                                                  for _ in range(max(1, self.policy.side_streams))], self.device)
+        self._sides, self._ln_tables, self._tn_tables = self.branch.sides, self.branch.ln_tables, self.branch.tn_tables      # never rebound
         self._main_stream = None       # set by TrainStep: the exchange / copy streams are chosen to run beside it too
-        self._side_rr = 0
-        self._side_q: List = []        # queued parameter-gradient launches (see _side_defer / _flush_side)
-        self._side_done = None         # completion event of the last batch issued to the branch
-        self._ln_jobs: List = []       # parked LayerNorm partial sums (part, dgamma, dbeta, nblk, C)
-        self._tn_jobs: List = []       # parked linear weight gradients of the current block (dY, X, dW, bias gradient)
-        self._tn_tables = {}
-        self._xkv_jobs: List = []      # parked weight gradients of the hoisted context projections of the current parameter region
-        self._ln_tables = {}
         self._hoisted: Dict[str, Act] = {}      # forward outputs computed ahead by grouped launches (name -> Act)
         self._group_tables = {}
-        self._side = self._sides[0]
-        # scheduling state (see _end_join, enter_micro_step); the data-parallel overlap's parameter side is the store's (params.py)
-        self._defer_join = False
-        self._pool_parity = 0
         self._after_tail_hook = None
         self._tape_mark = self._tape_mark1 = 0
-        self._events: list = []      # pool of fork / join events (ForkEvent, or torch.cuda.Event with policy.fork_events off)
-        self._ev_cursor = 0
         for slot in (2, 1, 0):
             ops.set_workspace_slot(slot); ops.workspace(self.device)
 
@@ -225,54 +213,13 @@ class AozoraUNet:
         if self._after_tail_hook is not None:
             self._after_tail_hook(k)
 
-    # ---- host launch tape support: stream / event operations of the launch sequence go through these two so that a
-    # recording (lib().recorder) captures them next to the ABI launches
-    def _ev_record(self, ev, stream):
-        ev.record(stream)
-        rec = lib().recorder
-        if rec is not None:
-            rec.append(Record(ev, stream))
-
-    def _st_wait(self, stream, ev):
-        ev.wait(stream)
-        rec = lib().recorder
-        if rec is not None:
-            rec.append(Wait(stream, ev))
-
-    def _live(self, fn, *args):
-        """Run fn(*args) now with recording suspended and put the call itself on the tape (state-dependent host logic)."""
-        L = lib()
-        rec, L.recorder = L.recorder, None
-        try:
-            fn(*args)
-        finally:
-            L.recorder = rec
-        if rec is not None:
-            rec.append(Live(fn, args))
-
-    def _end_join(self):
-        """End of a backward.  Default: the data chain waits for the parameter-gradient stream(s).  With
-        `_defer_join` (TrainStep(double_buffer=True), a non-final micro-step of an accumulation window) the branch is NOT
-        joined: its remaining weight-gradient products keep running under the next micro-step's forward, whose launches
-        write into the other activation pool; only an event is left for the next user of THIS pool."""
-        main = torch.cuda.current_stream()
-        evs = []
-        for sd in self._sides:
-            ev = torch.cuda.Event(); ev.record(sd); evs.append(ev)
-        if self._defer_join:
-            self.acts.leave_readers(self._pool_parity, evs)
-        else:
-            for ev in evs:
-                main.wait_event(ev)
-            self.acts.clear_readers()     # the in-order side stream(s) are fully drained now
-
     def enter_micro_step(self, parity, defer_join=False) -> int:
         """TrainStep, before a micro-step on activation pool `parity` issues anything: wait for the deferred weight-gradient work of the
         pool's previous user, replace the arena if that user found it too small, and note how this micro-step's backward ends
-        (_end_join).  -> the arena's generation (ActivationStore.prepare)."""
+        (GradBranch._end_join).  -> the arena's generation (ActivationStore.prepare)."""
         self.acts.wait_free(parity)
         gen = self.acts.prepare(parity)
-        self._defer_join, self._pool_parity = bool(defer_join), parity
+        self.branch.enter(parity, defer_join)
         return gen
 
     def set_lora_dropout_seed(self, seed: int):
@@ -305,146 +252,11 @@ class AozoraUNet:
         self.training = mode
         return self
 
-    # ------------------------------------------------------------------ fork / join ---------------
-    def _event(self):
-        if self._ev_cursor == len(self._events):
-            self._events.append(ForkEvent() if self.policy.fork_events else torch.cuda.Event())
-        ev = self._events[self._ev_cursor]
-        self._ev_cursor += 1
-        return ev
-
-    class _Side:
-        """with unet._fork(): ... launches go to the side stream (own workspace) and are joined on exit."""
-
-        def __init__(self, u):
-            self.u = u
-
-        def __enter__(self):
-            u = self.u
-            self.main = torch.cuda.current_stream()
-            if not u.concurrent_wgrad:
-                return self
-            k = u._side_rr % len(u._sides)
-            u._side_rr += 1
-            self.stream = u._sides[k]
-            ev = u._event(); u._ev_record(ev, self.main); u._st_wait(self.stream, ev)
-            u._side_used = True
-            self.ctx = torch.cuda.stream(self.stream); self.ctx.__enter__()
-            ops.set_workspace_slot(1 + k)
-            return self
-
-        def __exit__(self, *a):
-            u = self.u
-            if not u.concurrent_wgrad:
-                return False
-            ops.set_workspace_slot(0)
-            self.ctx.__exit__(*a)
-            self.done = u._event(); u._ev_record(self.done, self.stream)
-            return False
-
-        done = None
-
-        def join(self):
-            if self.u.concurrent_wgrad and self.done is not None:
-                self.u._st_wait(self.main, self.done)
-
-    def _fork(self):
-        return AozoraUNet._Side(self)
-
     # ------------------------------------------------------------------ tape helpers --------------
     def _wait_ready(self, a: Act):
         if a.ready is not None:
-            self._st_wait(torch.cuda.current_stream(), a.ready)
+            wait_event(torch.cuda.current_stream(), a.ready)
             a.ready = None
-
-    # ---- the parameter-gradient branch: weight / bias gradient launches are queued and issued in batches ----------------------
-    def _side_defer(self, fn):
-        if not self.concurrent_wgrad:
-            fn()
-        else:
-            self._side_q.append(fn)
-            if len(self._side_q) >= self.policy.side_batch:
-                self._flush_side()
-
-    def _finish_ln_jobs(self):
-        """Queue ONE finish launch for the parked LayerNorm partial sums (layernorm.bwd) on the parameter-gradient branch."""
-        jobs, self._ln_jobs = self._ln_jobs, []
-        if not jobs:
-            return
-        # keyed by everything a record holds: pools of different buckets hand out the same arena addresses for other shapes
-        key = tuple((p.data_ptr(), gw.data_ptr() if gw is not None else 0, gb.data_ptr() if gb is not None else 0, nblk, C)
-                    for p, gw, gb, nblk, C in jobs)
-        tab = self._ln_tables.get(key)
-        if tab is None:
-            rows_, blocks = [], 0
-            for part, gw, gb, nblk, C in jobs:
-                rows_.append([part.data_ptr(), gw.data_ptr() if gw is not None else 0, gb.data_ptr() if gb is not None else 0, nblk, C, blocks])
-                blocks += (C + 31) // 32
-            tab = (torch.tensor(rows_, dtype=torch.int64, device=self.device), len(rows_), blocks)
-            self._ln_tables[key] = tab
-        self._side_defer(lambda: ops.ln_param_finish_multi(tab[0], tab[1], tab[2]))
-
-    @staticmethod
-    def _linear_wgrad(dy, x, dW, bias_grad):
-        """dW += dY^T . X of a linear layer; the bias gradient (column sums of dY) rides on the same pass over dY."""
-        ops.gemm(dy, x, dW, trans_a=True, trans_b=False, accumulate=True, split_k=0, bias_grad=bias_grad)
-
-    def _queue_wgrads(self, jobs, grouped, tag=()):
-        """Queue parked linear weight gradients (dY, X, dW, bias gradient) on the parameter-gradient branch: as ONE grouped launch
-        whose job table is built once per operand set (`tag` keeps the keys of different callers apart), or one product each."""
-        if not grouped:
-            for job in jobs:
-                self._side_defer(lambda job=job: self._linear_wgrad(*job))
-            return
-        key = tag + tuple((dy.data_ptr(), xt.data_ptr(), GW.data_ptr(), bg.data_ptr() if bg is not None else 0, tuple(dy.shape), dy.stride(0),
-                           tuple(xt.shape), xt.stride(0), bg.numel() if bg is not None else 0) for dy, xt, GW, bg in jobs)
-        tab = self._tn_tables.get(key)
-        if tab is None:
-            tab = self._tn_tables[key] = ops.tn_group_table(jobs, self.device)
-        self._side_defer(lambda: ops.gemm_tn_grouped(*tab))
-
-    def _finish_tn_jobs(self):
-        """Queue the parked linear weight gradients on the parameter-gradient branch: as ONE grouped launch (every product over its
-        whole k-range on 128x128 tiles -- no fp32 slabs, no reduce launches, the tiles of all products fill the chip together) when
-        they add up to a chip-filling grid, else one split-K product each as before.  dY / X stay valid until the step ends: the
-        activation pool never re-uses a buffer inside a step and a buffer that is some layer's dY is never written again (acts.gbuf)."""
-        jobs, self._tn_jobs = self._tn_jobs, []
-        if jobs:
-            tiles = sum(((dy.shape[1] + 127) // 128) * ((xt.shape[1] + 127) // 128) for dy, xt, _, _ in jobs)
-            self._queue_wgrads(jobs, tiles >= self.policy.tn_group)
-
-    def _finish_xkv_jobs(self):
-        """The parked K / V projection weight gradients of a parameter region as ONE grouped launch on the branch (policy.xkv_group)."""
-        jobs, self._xkv_jobs = self._xkv_jobs, []
-        if jobs:
-            self._queue_wgrads(jobs, len(jobs) > 1, ("xkv",))
-
-    def _region_end(self):
-        """A parameter region's backward is through: everything parked for the parameter-gradient branch goes out."""
-        self._finish_ln_jobs()
-        self._finish_tn_jobs()
-        self._finish_xkv_jobs()
-        self._flush_side()
-
-    def _block_end(self):
-        """Tape entry placed at the START of a block's forward (so it runs AFTER the block's backward): the block's parked
-        parameter-gradient work goes out."""
-        self._finish_tn_jobs()
-        self._flush_side()
-
-    def _flush_side(self):
-        """Issue the queued parameter-gradient launches on the side stream behind ONE fork event; -> the completion event of
-        everything issued to the branch so far (the branch is one in-order stream per fork target; with an empty queue that is
-        the previous flush's event, which _side_defer may just have produced)."""
-        if not self._side_q:
-            return self._side_done
-        q, self._side_q = self._side_q, []
-        side = self._fork()
-        with side:
-            for fn in q:
-                fn()
-        self._side_done = side.done
-        return side.done
 
     # ------------------------------------------------------------------ layers --------------------
     def _bias_grad(self, dy: torch.Tensor, bname: Optional[str], n_real: int, rows_per_seg=None, seg_out: Optional[Act] = None):
@@ -488,7 +300,7 @@ class AozoraUNet:
                 if not x.need_grad:
                     self.adapters.du(lg, dy, du.t, rps)
                 self.adapters.wgrad(lg, x.t, u.t, dy, du.t, geom)
-            self._side_defer(wgrad)
+            self.branch.defer(wgrad)
 
     def linear(self, x: Act, wname: str, bname: Optional[str], residual: Optional[Act] = None,
                w_override: Optional[Tuple[torch.Tensor, torch.Tensor, bool]] = None, out: Optional[Act] = None,
@@ -548,7 +360,7 @@ class AozoraUNet:
             du = self._adapter_du_buf(lg, x)
             # DoRA: every consumer of dy but the bias and the residual reads dv = g dy (pool order independent of the freeze mask)
             dyv = self.acts.pool.get(tuple(dy.shape), BF16) if dora else dy
-            on_side = side_dgrad and self.policy.temb_side and self.concurrent_wgrad and len(self._sides) == 1
+            on_side = side_dgrad and self.policy.temb_side and self.branch.concurrent and len(self.branch.sides) == 1
             if dora and on_side:      # dy would be produced on the branch and read by az_dora_bwd_bf16 on the chain, unordered
                 raise AozoraError("DoRA on a layer whose data gradient runs on the parameter-gradient branch (side_dgrad) is not supported")
             if on_side:
@@ -563,27 +375,23 @@ class AozoraUNet:
                 if x.need_grad:
                     self.adapters.dora_bwd(lg, dy, v.t, dyv)
                 elif l_train or w_train:
-                    self._side_defer(lambda: self.adapters.dora_bwd(lg, dy, v.t, dyv))
+                    self.branch.defer(lambda: self.adapters.dora_bwd(lg, dy, v.t, dyv))
                 job = (dyv, x.t, GW, None)       # a trainable base weight takes dv; its bias the layer's own dy
                 if w_train and b_train:
-                    self._side_defer(lambda: self._bias_grad(dy, bname, N))
+                    self.branch.defer(lambda: self._bias_grad(dy, bname, N))
 
             def wgrad():        # parameter gradients run as a free-running branch beside the data-gradient chain
                 if w_train:
-                    self._linear_wgrad(*job)
+                    self.branch._linear_wgrad(*job)
                 elif b_train:
                     self._bias_grad(dy, bname, N)
-            if w_train and pre is not None and w_override is not None and rows <= 512 and self.policy.xkv_group and self.concurrent_wgrad and not on_side:
+            if w_train and pre is not None and w_override is not None and rows <= 512 and self.policy.xkv_group and self.branch.concurrent and not on_side:
                 # a hoisted context projection (K | V of a cross-attention): parked until the region's backward is through
-                self._xkv_jobs.append(job)
+                self.branch.park_xkv(job)
             elif w_train and self.policy.tn_group > 0 and 256 <= rows <= 8192 and not on_side:
-                # parked until the parked products add up to a chip-filling grid (attn2.to_out + attn2.to_q; attn1.to_out + to_q|k|v;
-                # the feed-forward ones are that large on their own), then ONE grouped launch, every product over its whole k-range
-                self._tn_jobs.append(job)
-                if sum(((j[0].shape[1] + 127) // 128) * ((j[1].shape[1] + 127) // 128) for j in self._tn_jobs) >= self.policy.tn_group:
-                    self._finish_tn_jobs()
+                self.branch.park_tn(job)      # ... until the parked products add up to a chip-filling grid, then ONE grouped launch
             elif w_train or b_train:
-                self._side_defer(wgrad)
+                self.branch.defer(wgrad)
             if lg is not None:
                 self._adapter_bwd(lg, l_train, x, u, dyv, du)
             if x.need_grad:
@@ -596,8 +404,8 @@ class AozoraUNet:
                     if lg is not None:
                         self.adapters.dgrad(lg, du.t, dx)         # dx += du A_cat, directly behind the base product
                 if on_side:
-                    self._side_defer(dgrad)
-                    x.ready = self._flush_side()
+                    self.branch.defer(dgrad)
+                    x.ready = self.branch.flush()
                 else:
                     dgrad()
             if residual is not None:   # dy becomes the residual's gradient (never written again: acts.gbuf)
@@ -665,9 +473,9 @@ class AozoraUNet:
                         self._bias_grad(dy, bname, Cout, rows_per_seg=Ho * Wo, seg_out=rowbias)
                     if self._trainable(wname):
                         ops.conv_wgrad(dy4, x4, self._gw[wname], stride=stride, cout_real=Cout, accumulate=True, split_k=0, upsample=upsample)
-            self._side_defer(wgrad)
+            self.branch.defer(wgrad)
             if need_seg:       # the time-embedding gradient is produced on the side stream and read by the chain soon: issue now
-                rowbias.ready = self._flush_side()
+                rowbias.ready = self.branch.flush()
             if lg is not None:
                 self._adapter_bwd(lg, l_train, x, u, dy, du, geom)
             if x.need_grad:
@@ -741,19 +549,19 @@ class AozoraUNet:
             if self.policy.ln_fused:                              # one pass over x / dy for dx and the gamma / beta gradients
                 if self.policy.ln_defer:
                     # ... whose per-block partial sums are parked: all LayerNorms of a parameter region are finished by ONE
-                    # launch on the parameter-gradient branch (_finish_ln_jobs) instead of one finish launch each on the chain.
+                    # launch on the parameter-gradient branch (GradBranch.finish_ln) instead of one finish launch each on the chain.
                     # (The buffer is taken whether or not the parameters are frozen: the pool's allocation order may not
                     # depend on the freeze mask.)
                     nblk = ops.ln_partial_blocks(rows)
                     part = self.acts.pool.get((nblk * C * 2,), F32)
                 if self.policy.ln_defer and (gw is not None or gb is not None):
                     ops.layernorm_bwd_partial(x.t, gam, stats, dy, dx, part, dx_add=add, nblk=nblk)
-                    self._ln_jobs.append((part, gw, gb, nblk, C))
+                    self.branch.park_ln((part, gw, gb, nblk, C))
                     return
                 ops.layernorm_bwd(x.t, gam, stats, dy, dx, gw, gb, dx_add=add)
                 return
             if gw is not None or gb is not None:       # gamma / beta gradients leave the data-gradient chain
-                self._side_defer(lambda: ops.layernorm_bwd(x.t, gam, stats, dy, None, gw, gb))
+                self.branch.defer(lambda: ops.layernorm_bwd(x.t, gam, stats, dy, None, gw, gb))
             ops.layernorm_bwd(x.t, gam, stats, dy, dx, None, None, dx_add=add)
         self._tape.append(bwd)
         return y
@@ -820,7 +628,7 @@ class AozoraUNet:
                 # are not issued at all while to_k | to_v are frozen
                 ops.attn_bwd(q3, k3, v3, o3, do3, lse, delta, dq3, dk3, dv3, heads, scale, parts=3)
                 if kv_train:
-                    self._side_defer(lambda: ops.attn_bwd(q3, k3, v3, o3, do3, lse, delta, dq3, dk3, dv3, heads, scale, parts=4))
+                    self.branch.defer(lambda: ops.attn_bwd(q3, k3, v3, o3, do3, lse, delta, dq3, dk3, dv3, heads, scale, parts=4))
             else:
                 ops.attn_bwd(q3, k3, v3, o3, do3, lse, delta, dq3, dk3, dv3, heads, scale)
         self._tape.append(bwd)
@@ -905,7 +713,7 @@ class AozoraUNet:
         return out
 
     def tblock(self, h: Act, B, T, ctx: Act, ctx_len, pre) -> Act:
-        self._tape.append(self._block_end)       # runs AFTER this block's backward: its parameter gradients go out as one batch
+        self._tape.append(self.branch.block_end)       # runs AFTER this block's backward: its parameter gradients go out as one batch
         n = self.layernorm(h, pre + ".norm1")
         h = self.attention(n, B, T, pre + ".attn1", None, 0, residual=h)
         n = self.layernorm(h, pre + ".norm2")
@@ -924,7 +732,7 @@ class AozoraUNet:
 
     def transformer(self, x: Act, geom, ctx: Act, ctx_len, pre, n_layers, out: Optional[Act] = None) -> Act:
         B, H, W_ = geom
-        self._tape.append(self._block_end)
+        self._tape.append(self.branch.block_end)
         n = self.groupnorm(x, geom, pre + ".norm", 1e-6, False)
         h = self.linear(n, pre + ".proj_in.weight", pre + ".proj_in.bias")
         for i in range(n_layers):
@@ -932,7 +740,7 @@ class AozoraUNet:
         return self.linear(h, pre + ".proj_out.weight", pre + ".proj_out.bias", residual=x, out=out)
 
     def resnet(self, x: Act, geom, emb_s: Act, pre, out: Optional[Act] = None) -> Act:
-        self._tape.append(self._block_end)
+        self._tape.append(self.branch.block_end)
         n1 = self.groupnorm(x, geom, pre + ".norm1", 1e-5, True)
         t = self.linear(emb_s, pre + ".time_emb_proj.weight", pre + ".time_emb_proj.bias", pre=self._hoisted.pop(pre + ".temb", None), side_dgrad=True)
         h, _ = self.conv(n1, geom, pre + ".conv1.weight", pre + ".conv1.bias", rowbias=t)
@@ -996,9 +804,8 @@ class AozoraUNet:
     # ------------------------------------------------------------------ whole model ---------------
     def __del__(self):
         try:
-            for ev in getattr(self, "_events", []):
-                if isinstance(ev, ForkEvent):
-                    ev.destroy()
+            if getattr(self, "branch", None) is not None:
+                self.branch.reset_events()
             if getattr(self, "_ctx", None):
                 lib()._fn["az_destroy"](self._ctx)
                 self._ctx = None
@@ -1016,14 +823,17 @@ class AozoraUNet:
     def _arena_of(self, parity) -> _Arena: return self.acts.arena_of(parity)
     def _settle_arena(self, arena: _Arena): return self.acts.settle(arena)
 
+    # The parameter-gradient branch (branch.py) has one switch that callers set on the UNet; the layers call self.branch directly.
+    concurrent_wgrad = property(lambda self: self.branch.concurrent, lambda self, on: setattr(self.branch, "concurrent", on))
+
     def _arena_replaced(self, arena: _Arena):
         """The store replaces `arena` (ActivationStore.settle: the device is synchronised, the arena's pools are dropped, the old
         memory is still held): the executor's own holders of its addresses let go -- the per-step lists, then the launch tapes /
         graphs of the TrainStep objects."""
-        self._tape, self._side_q, self._ln_jobs, self._tn_jobs, self._xkv_jobs, self._hoisted = [], [], [], [], [], {}
-        # the pointer tables (_ln_tables, _tn_tables, _group_tables) stay: recorded launches of the OTHER parity's buckets hold their
-        # raw addresses, and their keys carry everything a record holds, so an entry made of dead addresses can only be found
-        # again by a launch that means exactly those addresses and shapes
+        self._tape, self._hoisted = [], {}
+        self.branch.drop()
+        # _group_tables stays, like the branch's pointer tables (GradBranch.drop): recorded launches of the OTHER parity's buckets
+        # hold their raw addresses
         for client in list(self.acts.clients):
             client._arena_replaced(arena)
 
@@ -1044,15 +854,8 @@ class AozoraUNet:
         self.acts.begin(key, recording=lib().recorder is not None)
         self.refresh_transposed()
         self._tape = []
-        self._ev_cursor = 0
-        self._side_used = False
-        self._side_rr = 0
-        self._side_q = []
-        self._side_done = None
-        self._ln_jobs = []
-        self._tn_jobs = []
-        self._xkv_jobs = []
         self._hoisted = {}
+        self.branch.begin()
 
     def forward_nhwc(self, x8: torch.Tensor, t_f32: torch.Tensor, ctx: torch.Tensor, pooled: torch.Tensor,
                      time_ids_f32: torch.Tensor) -> Act:
@@ -1068,7 +871,7 @@ class AozoraUNet:
         T = cfg.time_embed_dim
         # forward: the data chain has the CUs (and their LDS) to itself (kept so even with deferred weight-gradient work
         # around: measured 0.851 vs 0.835 it/s)
-        self._live(lib().call, "az_gemm_set_exclusive", 1)
+        run_live(lib().call, "az_gemm_set_exclusive", 1)
         # ---- embeddings (a7.1) ----
         tsin = self.acts.new(B, ch[0], need_grad=False)
         ops.timestep_embed(t_f32, ch[0], tsin.t)
@@ -1119,7 +922,7 @@ class AozoraUNet:
         if self.dora is not None:
             # the magnitudes and their gains lie behind conv_out.bias (region 2: updated on the background stream, the norm pass behind it)
             # and are read from the first transformer of the down path on: their region's event is taken up front
-            self._live(self.wait_region_params, 2)
+            run_live(self.wait_region_params, 2)
         h, _ = self.conv(xin, geom, "conv_in.weight", "conv_in.bias", out=skip_dest(B * H * W_, ch[0]))
         self._hoist_shared_input_linears(self._region_blocks(0), ctx_a, emb_s)
         skips.append(h)
@@ -1127,7 +930,7 @@ class AozoraUNet:
             pre = f"down_blocks.{i}"
             if i == nlev - 1:
                 self._tape_mark1 = len(self._tape)     # backward entries in [mark1, mark) belong to the last down block (region 1)
-                self._live(self.wait_region_params, 1)  # DP overlap: region 1's all-gather must have landed by now
+                run_live(self.wait_region_params, 1)  # DP overlap: region 1's all-gather must have landed by now
                 self._hoist_shared_input_linears(self._region_blocks(1), ctx_a, emb_s)
             rows = geom[0] * geom[1] * geom[2]
             for j in range(lpb):
@@ -1145,7 +948,7 @@ class AozoraUNet:
                 skips.append(h)
         # ---- mid ----
         self._tape_mark = len(self._tape)       # backward entries >= mark belong to mid / up / head-out (the "tail" region)
-        self._live(self.wait_region_params, 2)  # DP overlap: the tail parameters' all-gather must have landed by now
+        run_live(self.wait_region_params, 2)  # DP overlap: the tail parameters' all-gather must have landed by now
         self._hoist_shared_input_linears(self._region_blocks(2), ctx_a, emb_s)
         h = self.resnet(h, geom, emb_s, "mid_block.resnets.0")
         h = self.transformer(h, geom, ctx_a, L, "mid_block.attentions.0", cfg.transformer_layers[-1])
@@ -1175,21 +978,19 @@ class AozoraUNet:
         """dpred8 (B,H,W,8) bf16: d(loss)/d(pred), channels >= out_channels zero. Gradients are
         ACCUMULATED into the flat gradient buffer."""
         lib().call("az_gemm_set_exclusive", 0)       # the parameter-gradient stream shares the CUs from here on
-        self._live(self._wait_wt_ready)              # an asynchronous W^T refresh must have finished before the first dgrad
+        run_live(self._wait_wt_ready)              # an asynchronous W^T refresh must have finished before the first dgrad
         B, H, W_, Cp = dpred8.shape
         pred.g = dpred8.view(B * H * W_, Cp)
         mark, mark1 = self._tape_mark, self._tape_mark1
         self._after_tail_hook = after_tail
         for idx in range(len(self._tape) - 1, -1, -1):
             if idx == mark - 1:
-                self._region_end()
-                self._live(self._region_hook, 2)   # every gradient of region 2 has been issued (main + side stream)
+                self.branch.region_end()
+                run_live(self._region_hook, 2)   # every gradient of region 2 has been issued (main + side stream)
             if idx == mark1 - 1:
-                self._region_end()
-                self._live(self._region_hook, 1)   # ... and now those of region 1 (the last down block)
+                self.branch.region_end()
+                run_live(self._region_hook, 1)   # ... and now those of region 1 (the last down block)
             self._tape[idx]()
-        self._region_end()
+        self.branch.region_end()
         self._tape = []
-        if self.concurrent_wgrad and self._side_used:      # join the parameter-gradient branches (or let them run on)
-            self._live(self._end_join)
-            self._side_used = False
+        self.branch.join()      # the parameter-gradient branches, if any was forked (or let them run on)

@@ -184,20 +184,22 @@ def test_arena_is_bounded_by_the_largest_bucket(order):
 
 def test_replacing_an_arena_keeps_what_other_parities_recorded(monkeypatch):
     """ActivationStore.settle with no device, its on_replace the executor's own hook (AozoraUNet._arena_replaced on a bare object
-    that has only the fields the hook touches): the device is synchronised BEFORE anything is released, the TrainStep objects let
+    that has only the fields the hook touches, its parameter-gradient branch a real GradBranch): the device is synchronised BEFORE anything is released, the TrainStep objects let
     go before the old arena does, only pools of the replaced arena are dropped -- and the pointer tables stay: launch tapes of the
     other parity hold their raw addresses (they were once cleared here, and a double-buffered run replayed a tape over freed
     tables)."""
-    from aozora_sdxl_training_amd.unet import AozoraUNet
+    from aozora_sdxl_training_amd.branch import GradBranch
+    from aozora_sdxl_training_amd.unet import AozoraUNet, ExecPolicy
     log = []
     monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: log.append("sync"))
     u = object.__new__(AozoraUNet)
     s = u.acts = ActivationStore("cpu", on_replace=u._arena_replaced)
     assert (s.pools, s.pool, s.arenas, s.generation, s.deferred) == ({}, None, {}, 0, {})
     s.leave_readers(0, ["ev"])
-    u._tape, u._side_q, u._ln_jobs, u._tn_jobs, u._xkv_jobs, u._hoisted = [1], [1], [1], [1], [1], {"a": 1}
+    b = u.branch = GradBranch(ExecPolicy(), s, [], "cpu")
+    u._tape, b.q, b.ln_jobs, b.tn_jobs, b.xkv_jobs, u._hoisted = [1], [1], [1], [1], [1], {"a": 1}
     table = torch.zeros(4, dtype=torch.int64)
-    u._ln_tables, u._tn_tables, u._group_tables = {"k": table}, {"k": table}, {"k": table}
+    b.ln_tables["k"], b.tn_tables["k"], u._group_tables = table, table, {"k": table}
 
     class Client:
         def _arena_replaced(self, arena):
@@ -211,7 +213,7 @@ def test_replacing_an_arena_keeps_what_other_parities_recorded(monkeypatch):
         _run(s.pools[key], shapes)
     assert s.prepare(0) == 1 and log == ["sync", ("client", 0)]
     assert not s.has_deferred()
-    assert (u._tape, u._side_q, u._ln_jobs, u._tn_jobs, u._xkv_jobs, u._hoisted) == ([], [], [], [], [], {})
+    assert (u._tape, b.q, b.ln_jobs, b.tn_jobs, b.xkv_jobs, u._hoisted) == ([], [], [], [], [], {})
     assert s.prepare(1) == 1 and s.generation == 2
     p0, p1 = s.pools[(2, 16, 16, 77, 0)], s.pools[(2, 16, 16, 77, 1)]
     _run(p0, SMALL); _run(p1, MID)
@@ -224,7 +226,7 @@ def test_replacing_an_arena_keeps_what_other_parities_recorded(monkeypatch):
     assert s.prepare(0) == 2 and log == ["sync", ("client", _need(SMALL))]
     assert s.generation == 3 and a0.capacity == _need(LARGE) and a1.generation == 1
     assert not p0.bufs and [b.data_ptr() for b in p1.bufs] == addr1   # parity 1 keeps its views
-    assert u._ln_tables == {"k": table} and u._tn_tables == {"k": table} and u._group_tables == {"k": table}
+    assert b.ln_tables == {"k": table} and b.tn_tables == {"k": table} and u._group_tables == {"k": table}
     assert s.activation_bytes() == {"arena": {0: _need(LARGE), 1: _need(MID)}, "generation": 3,
                                     "need": {(2, 16, 16, 77, 0): _need(SMALL), (2, 16, 16, 77, 1): _need(MID), (2, 24, 24, 77, 0): _need(LARGE)}}
     # ... and the UNet's forwarders and properties read the same store

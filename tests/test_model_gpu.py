@@ -755,22 +755,19 @@ def test_fork_events_order_two_streams_and_equal_torch_events_bitwise(setup):
     def window(fork, native, fuse=0):
         saved = (unet.policy.fork_events, unet.policy.native_tape, unet.policy.fuse_records)
         unet.policy.fork_events, unet.policy.native_tape, unet.policy.fuse_records = fork, native, fuse
-        unet._pools.clear(); unet._events = []; unet._ev_cursor = 0
+        unet._pools.clear(); unet.branch.reset_events()
         try:
             step = TrainStep(unet, mode="epsilon", grad_accum=3, use_graph=False)
             unet.zero_grad()
             ls = [step.micro_step(*args).item() for _ in range(3)]      # eager + recording, then two replays
             step.synchronize()
-            assert unet._events and all(isinstance(e, ForkEvent) == fork for e in unet._events)
+            assert unet.branch.events and all(isinstance(e, ForkEvent) == fork for e in unet.branch.events)
             if fuse:      # the peephole really rewrote the tape: records became stop events of the kernels in front of them
                 assert step.last_bucket.fused_records > 10
             return ls, unet.gflat.clone()
         finally:
             unet.policy.fork_events, unet.policy.native_tape, unet.policy.fuse_records = saved
-            for e in unet._events:
-                if isinstance(e, ForkEvent):
-                    e.destroy()
-            unet._pools.clear(); unet._events = []; unet._ev_cursor = 0
+            unet._pools.clear(); unet.branch.reset_events()
     ref_l, ref_g = window(False, True)
     for fork, native, fuse in ((True, True, 0), (True, False, 0), (True, True, 2), (True, False, 2), (True, True, 1)):
         l, g = window(fork, native, fuse)
@@ -822,3 +819,29 @@ def test_the_activation_store_is_the_only_holder_of_its_state(setup):
     ab = unet.activation_bytes()
     assert ab["generation"] == 1 and unet.generation == 1 and unet.acts.generation == 1
     assert ab["arena"] == {0: ab["need"][(1, 8, 8, 77, 0)]}
+
+
+@pytest.mark.gpu
+def test_the_gradient_branch_is_the_only_holder_of_its_state(setup):
+    """AozoraUNet shows the streams and the two pointer tables of its GradBranch (branch.py) as the same objects and holds nothing
+    else of the branch: after a micro-step the queue, the parked lists, the event pool and the switches live on the branch alone,
+    the branch really forked, and `concurrent_wgrad` is a view of `branch.concurrent`."""
+    from aozora_sdxl_training_amd.train_step import TrainStep
+    pc, oc, params, unet = setup
+    lat, noise, ctx, pooled, tid, ts, jit = _inputs(1, 8, 8, pc)
+    step = TrainStep(unet, mode="epsilon", grad_accum=1, use_graph=False)
+    unet.zero_grad()
+    assert math.isfinite(step.micro_step(lat.to(DEV), noise.to(DEV), ts, ctx.to(DEV), pooled.to(DEV), tid.to(DEV), jit).item())
+    step.synchronize()
+    b = unet.branch
+    assert unet._sides is b.sides and unet._ln_tables is b.ln_tables and unet._tn_tables is b.tn_tables
+    for name in ("_side_q", "_side_done", "_side_used", "_side_rr", "_ln_jobs", "_tn_jobs", "_xkv_jobs", "_events", "_ev_cursor",
+                 "_defer_join", "_pool_parity", "concurrent_wgrad"):
+        assert name not in unet.__dict__, name
+    assert b.events, "the branch never forked"
+    assert unet.concurrent_wgrad is True and b.concurrent is True
+    try:
+        unet.concurrent_wgrad = False
+        assert b.concurrent is False and unet.concurrent_wgrad is False and "concurrent_wgrad" not in unet.__dict__
+    finally:
+        unet.concurrent_wgrad = True
