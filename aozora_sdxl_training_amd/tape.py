@@ -38,7 +38,7 @@ _KERNEL_ENTRIES = frozenset({
     "az_transpose_multi_bf16", "az_f32_to_bf16", "az_timestep_embed", "az_nchw_to_nhwc_pad", "az_nhwc_to_nchw", "az_noise_target",
     "az_mse_loss_fwd_bwd", "az_sumsq_bf16", "az_sumsq", "az_clip_coef", "az_adamw_flat", "az_adamw_flat_ex", "az_adamw_flat_sr", "az_scale_bf16",
     "az_scale_f32", "az_stage_inputs", "az_adamw8bit_step", "az_ema_flat", "az_adamw_flat_master", "az_robust_loss_fwd_bwd", "az_adamw_flat_seg",
-    "az_noise_shape", "az_noise_target_ex", "az_prodigy_begin", "az_prodigy_moments", "az_prodigy_finish", "az_prodigy_apply",
+    "az_noise_shape", "az_noise_target_ex", "az_prodigy_begin", "az_prodigy_moments", "az_prodigy_finish", "az_prodigy_apply", "az_adafactor_step",
     "az_lora_down_bf16", "az_lora_up_bf16", "az_lora_wgrad_bf16", "az_lora_up_geglu_bf16",
     "az_lora_conv_down_bf16", "az_lora_conv_dgrad_bf16", "az_lora_conv_wgrad_bf16", "az_lora_dropout_bf16", "az_lora_max_norm_bf16",
     "az_dora_norm_bf16", "az_dora_scale_bf16", "az_dora_bwd_bf16"})

@@ -26,7 +26,7 @@ from .ema import EmaWeights, read_options as _ema_options
 from .loss import fold_min_snr, parse_loss_type
 from .noise import draw_aux, parse_noise_mode
 from . import param_groups as pgroups
-from .optimizers import PagedAdamW8bit, Prodigy, RavenAdamW, TitanAdamW
+from .optimizers import Adafactor, PagedAdamW8bit, Prodigy, RavenAdamW, TitanAdamW
 from .schedule import (CustomCurveLRScheduler, TimestepSampler, ddpm_alphas_cumprod, generate_noise, make_time_ids,
                        seeded_torch_generator, timestep_loss_curve_from_config, trainable_mask)
 from .telemetry import Reporter
@@ -53,7 +53,16 @@ _PRODIGY_GROUPS_REFUSAL = ("param_groups is an option of raven, titan and paged_
                            "trainable elements and takes one group -- remove the key from PRODIGY_PARAMS")
 _PRODIGY_KEYS = ("betas", "beta3", "eps", "weight_decay", "use_bias_correction", "safeguard_warmup", "d0", "d_coef", "growth_rate",
                  "ema_decay", "ema_warmup")
-_PARAMS_KEY = {"titan": "TITAN_PARAMS", "paged_adamw_8bit": "PAGED_ADAMW_8BIT_PARAMS", "prodigy": "PRODIGY_PARAMS"}
+_ADAFACTOR_DP_REFUSAL = ("adafactor runs at one rank only: its row and column means and the per-tensor RMS of the update run over WHOLE "
+                         "tensors, which the data-parallel shards cut -- data-parallel training supports raven and titan")
+_ADAFACTOR_GROUPS_REFUSAL = ("param_groups is an option of raven, titan and paged_adamw_8bit: optimizers.Adafactor takes one group (its "
+                             "per-tensor scalars are dealt from one descriptor table) -- remove the key from ADAFACTOR_PARAMS")
+_ADAFACTOR_MASTER_REFUSAL = ("master_weights is an option of raven and titan (RAVEN_PARAMS / TITAN_PARAMS): optimizers.Adafactor keeps no "
+                             "fp32 master copy yet -- \"stochastic_rounding\": true is its answer to updates below the bf16 spacing; remove "
+                             "the key from ADAFACTOR_PARAMS")
+_ADAFACTOR_KEYS = ("eps", "clip_threshold", "decay_rate", "beta1", "weight_decay", "scale_parameter", "relative_step", "warmup_init",
+                   "stochastic_rounding", "ema_decay", "ema_warmup")
+_PARAMS_KEY = {"titan": "TITAN_PARAMS", "paged_adamw_8bit": "PAGED_ADAMW_8BIT_PARAMS", "prodigy": "PRODIGY_PARAMS", "adafactor": "ADAFACTOR_PARAMS"}
 
 
 def _momentum_dtype(v):
@@ -110,6 +119,8 @@ def _master_option(config) -> bool:
             raise ValueError(_MASTER_8BIT_REFUSAL)
         return False
     if kind == "prodigy":           # its own master copy, always (prodigy_options refuses the key)
+        return False
+    if kind == "adafactor":         # no master copy (adafactor_options refuses the key)
         return False
     hp = dict(getattr(config, "TITAN_PARAMS" if kind == "titan" else "RAVEN_PARAMS", {}) or {})
     if not _as_bool(hp.get("master_weights", False)):
@@ -174,6 +185,46 @@ def prodigy_options(config, world: int = 1) -> dict:
     return kw
 
 
+def adafactor_options(config, world: int = 1) -> dict:
+    """ADAFACTOR_PARAMS (config.py: `<mode>_adafactor_params` of the preset's active block, default {}) -> the keywords of
+    optimizers.Adafactor, lr excepted (that is the curve's, as for the other optimizers; ignored under relative_step) and with the
+    stochastic-rounding seed taken from SEED.  Refuses, before anything is allocated: more than one rank, param_groups, master_weights,
+    an unknown key (a typo must not silently train the default), a value that cannot be read, and what the constructor refuses
+    (warmup_init without relative_step, clip_threshold <= 0, beta1 outside [0, 1)).  Absent keys take the optimizer's defaults
+    (INTEGRATION.md "The Adafactor optimizer")."""
+    from .optimizers.adafactor import check_options
+    if world > 1:
+        raise ValueError(_ADAFACTOR_DP_REFUSAL)
+    hp = dict(getattr(config, "ADAFACTOR_PARAMS", None) or {})
+    for key, why in (("param_groups", _ADAFACTOR_GROUPS_REFUSAL), ("master_weights", _ADAFACTOR_MASTER_REFUSAL)):
+        if key in hp:
+            raise ValueError(why)
+    unknown = sorted(k for k in hp if k not in _ADAFACTOR_KEYS)
+    if unknown:
+        raise ValueError(f"ADAFACTOR_PARAMS holds unknown key(s) {unknown}: this build reads {sorted(_ADAFACTOR_KEYS)} (the learning rate "
+                         "comes from LR_CUSTOM_CURVE)")
+    kw = {k: hp[k] for k in _ADAFACTOR_KEYS[:9] if k in hp and (hp[k] is not None or k == "beta1")}
+    try:
+        for k in ("clip_threshold", "decay_rate", "weight_decay"):
+            if k in kw:
+                kw[k] = float(kw[k])
+        if kw.get("beta1") is not None:
+            kw["beta1"] = float(kw["beta1"])
+        if "eps" in kw:
+            kw["eps"] = tuple(float(e) for e in kw["eps"])
+            if len(kw["eps"]) != 2:
+                raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"ADAFACTOR_PARAMS: a numeric option cannot be read as a number (eps: two numbers): {hp}") from None
+    for k in ("scale_parameter", "relative_step", "warmup_init", "stochastic_rounding"):
+        if k in kw:
+            kw[k] = _as_bool(kw[k])
+    check_options(kw.get("eps", (1e-30, 1e-3)), kw.get("clip_threshold", 1.0), kw.get("decay_rate", -0.8), kw.get("beta1"),
+                  kw.get("weight_decay", 0.0), kw.get("scale_parameter", False), kw.get("relative_step", False), kw.get("warmup_init", False))
+    kw["sr_seed"] = int(getattr(config, "SEED", 0) or 0)
+    return kw
+
+
 def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = None, num_workers: Optional[int] = None):
     """Run config.MAX_TRAIN_STEPS micro-steps.  Returns dict(losses, grad_norms, lrs, micro_step, optimizer_step, saved).
 
@@ -192,6 +243,9 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     # refused, before anything is allocated
     prodigy = kind == "prodigy"
     prodigy_kw = prodigy_options(config, world) if prodigy else None
+    # OPTIMIZER_TYPE "adafactor" (optimizers.Adafactor; not in the reference): likewise
+    adafactor = kind == "adafactor"
+    adafactor_kw = adafactor_options(config, world) if adafactor else None
     # "ema_decay" [, "ema_warmup"] in the ACTIVE optimizer's dictionary: an fp32 EMA of the trainable weights (ema.py; not in the
     # reference, absent = off).  Read first: an invalid value is refused before anything is allocated.
     ema_decay, ema_warmup = _ema_options(getattr(config, _PARAMS_KEY.get(kind, "RAVEN_PARAMS"), None))
@@ -207,7 +261,7 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
     # "param_groups" in the active optimizer's dictionary (param_groups.py; not in the reference's trainer, absent or [] = off): the rules
     # are read, and what they do not combine with refused, before anything is allocated.  Like LOSS_TYPE they go into nothing that is
     # saved: a resumed run reads them from the preset again.
-    group_rules = [] if prodigy else pgroups.option(config)
+    group_rules = [] if (prodigy or adafactor) else pgroups.option(config)
     GA = int(config.GRADIENT_ACCUMULATION_STEPS)
     mode = getattr(config, "PREDICTION_TYPE", "epsilon")
     # LOSS_TYPE (loss.parse_loss_type; the reference's GUI offers "MSE" only): read before anything is allocated.  It goes into nothing
@@ -296,6 +350,23 @@ def train(config, unet=None, device="cuda:0", reporter: Optional[Reporter] = Non
             if lr0 < 1e-2:
                 print(f"INFO: prodigy: the largest learning rate of LR_CUSTOM_CURVE is {lr0:g}.  Prodigy's learning rate is a MULTIPLIER of its own "
                       "step-size estimate and belongs near 1 (a warm-up to 1.0 and a decay); the reference's AdamW-scale curve of 8e-7 would train nothing")
+    elif adafactor:
+        # likewise: expose_grads -> clip_grad_norm_ -> step (five launches from one descriptor table in HIP, nothing read back)
+        curve0 = getattr(config, "LR_CUSTOM_CURVE", [])
+        lr0 = max(p_[1] for p_ in curve0) if curve0 else config.LEARNING_RATE
+        optimizer = Adafactor(params, lr=lr0, **adafactor_kw)
+        if rank == 0:
+            shown = {k: v for k, v in optimizer.param_groups[0].items() if k not in ("params", "lr")}
+            print(f"INFO: OPTIMIZER_TYPE adafactor is ON ({shown}; {optimizer.state_bytes} bytes of fp32 state: row and column second moments, "
+                  f"full ones for vectors{', exp_avg' if adafactor_kw.get('beta1') is not None else ''}): an optimizer outside the reference; "
+                  "arithmetic of transformers.optimization.Adafactor, pinned by tests/golden/adafactor_golden.pt")
+            if adafactor_kw.get("relative_step"):
+                print("INFO: adafactor: relative_step is ON: the step size is min(1e-2 or 1e-6 * step, 1 / sqrt(step)) of the optimizer step, "
+                      "LR_CUSTOM_CURVE is ignored by the update and the reported learning rate is the curve's")
+            elif not adafactor_kw.get("stochastic_rounding") and lr0 < 1e-4:
+                print(f"INFO: adafactor: the largest learning rate of LR_CUSTOM_CURVE is {lr0:g} and stochastic_rounding is off.  Adafactor's "
+                      "update is at most about lr per element; half a bf16 spacing of a 0.02-sized weight is 6e-5, so with round-to-nearest "
+                      "the parameters do not move at all -- set \"stochastic_rounding\": true in ADAFACTOR_PARAMS")
     elif not host_titan:
         # The flat fused optimizer (one rank: no collectives): m / v resident in HBM (or, RAVEN_STATE_ON_HOST, prefetched under the
         # window's last micro-step and written back under the next window), update of the whole flat range in one launch per
@@ -707,7 +778,7 @@ def main(argv=None) -> int:
     (gui.py:5930-5975), here for the native step.  One process per GPU: started by torch.distributed.run (RANK / WORLD_SIZE /
     LOCAL_RANK in the environment) the ranks form an RCCL group and config.BATCH_SIZE is the GLOBAL micro-batch.
     Out of scope, refused with a message instead of being attempted: the Anima DiT mode, offline VAE / text-encoder caching
-    (the cache must exist), fp16 mixed precision and paged_adamw_8bit or prodigy under data parallel."""
+    (the cache must exist), fp16 mixed precision and paged_adamw_8bit, prodigy or adafactor under data parallel."""
     import os
     import sys
     from .config import TrainingConfig
@@ -725,12 +796,14 @@ def main(argv=None) -> int:
         lora_spec = lora_mod.options(config, int(os.environ.get("WORLD_SIZE", "1")), cfg=model_cfg)[0]
         if str(config.OPTIMIZER_TYPE).lower() == "prodigy":
             prodigy_options(config, int(os.environ.get("WORLD_SIZE", "1")))
+        elif str(config.OPTIMIZER_TYPE).lower() == "adafactor":
+            adafactor_options(config, int(os.environ.get("WORLD_SIZE", "1")))
         else:
             pgroups.option(config)
     except ValueError as e:
         print(f"ERROR: {e}.")
         return 2
-    if str(config.OPTIMIZER_TYPE).lower() not in ("raven", "titan", "paged_adamw_8bit", "prodigy"):
+    if str(config.OPTIMIZER_TYPE).lower() not in ("raven", "titan", "paged_adamw_8bit", "prodigy", "adafactor"):
         raise ValueError(f"Unsupported optimizer type: '{config.OPTIMIZER_TYPE}'")          # train.py:2290
     if str(config.OPTIMIZER_TYPE).lower() == "paged_adamw_8bit" and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         print(f"ERROR: {_ADAMW8_DP_REFUSAL}.")

@@ -524,6 +524,41 @@ int az_prodigy_moments(long n, const void* w, const void* p0, const void* g, int
 int az_prodigy_finish(long npartials, const void* partials, void* dstate, void* consts, void* stream);
 /* ref: not in the reference; stands where optimizer.step() does, train.py:2783 */
 int az_prodigy_apply(long n, void* p, void* w, const void* m, const void* v, const void* consts, void* stream);
+/* Adafactor (arXiv 1804.04235; an optimizer the reference does not have -- INTEGRATION.md "The Adafactor optimizer" states the
+ * arithmetic, that of transformers.optimization.Adafactor.step on logical tensor shapes, in full; tests/adafactor_ref.py restates it in
+ * float64): factored second moments (row and column vectors) for tensors of two or four dimensions, a full second moment for vectors,
+ * the update clipped per tensor by its own RMS.  az_adafactor_step is one whole optimizer step in FIVE launches on one stream whatever
+ * ntensors is (three when the table holds no matrix), no copy to the host, no synchronisation, no floating-point atomics: every sum
+ * has a fixed order, the per-tensor sums of u^2 and p^2 are fp64, a step is bit-reproducible.
+ *   desc (int64 words, az_adafactor_geometry(0) = 24 per row, one row per tensor, the SAME table on the host (desc_host, checked in full
+ *     before anything is launched) and on the device (desc, read by the kernels)): class (0 vector, 1 matrix, 2 batch of little
+ *     matrices), flags (1 = 16-byte accesses: p and g 16-byte aligned, C, the row stride and sr0 multiples of 8), p, g (addresses of
+ *     bf16 storage, read-write and read), batch extents nb0, nb1 with strides sb0, sb1, R with row stride sr, C with column stride sc
+ *     (strides in elements), state offsets of row (or v), col and exp_avg (fp32 elements of `state`; exp_avg in logical order, unused
+ *     without beta1), first workgroup and workgroup count of passes 1 / 3 / 5, first workgroup and count of pass 2, offset of the column
+ *     partials in `scratch` (stripes x C), offset of the C column factors and, behind them, the R row factors in `fac`, sr0 (flat offset of the tensor's first
+ *     element: stochastic rounding draws the bits of element sr0 + storage offset), logical element count, one spare word.
+ *     A matrix is nb0 = nb1 = 1, sc = 1 and takes ceil(R / geometry(1)) workgroups (row stripes) and ceil(C / geometry(4)) + 1 of pass 2;
+ *     a vector is R = 1, C = n and takes ceil(n / geometry(2)); a batch has R = C in {1, 3}, one thread per (b0, b1), and takes
+ *     ceil(nb0 nb1 / geometry(3)).  Matrices come first in the table; the numbering is cumulative in table order.
+ *   state, scratch, fac (device fp32, 16-byte aligned, with their element counts: every offset of the table is checked against them),
+ *   partials (device fp64, two per workgroup of pass 1), tsc (device fp32, four per tensor: clip denominator, lr_t, weight_decay lr_t,
+ *   RMS(u)).
+ *   hyper (HOST fp64[16], read during the call): beta2t, lr (the relative step where that is on), eps1, eps2, clip_threshold, beta1
+ *     (negative = none), weight_decay, scale_parameter (0 / 1), stochastic rounding (0 / 1), seed, step (>= 1), Philox domain.  beta2t,
+ *     1 - beta2t, beta1, 1 - beta1 are rounded once to fp32; lr_t = max(eps2, RMS(p)) lr (or lr) is formed in fp64 on the device and
+ *     rounded once.
+ * Per element: upd = g g + eps1; row / col / v = old beta2t + (1 - beta2t) mean; u = ((1 / sqrt(row / mean(row))) (1 / sqrt(col))) g or
+ * (1 / sqrt(v)) g; u = u / max(1, RMS(u) / clip); u = lr_t u; with beta1 m = m beta1 + (1 - beta1) u, u = m; with weight decay
+ * p = p - (weight_decay lr_t) p; p = p - u, rounded ONCE to bf16: to nearest even, or stochastically with the Philox layout of
+ * az_adamw_flat_sr.  Elements outside the logical tensor (channel padding, slot padding) are neither read nor written.
+ * ntensors == 0 returns 0 without a launch; a negative count, a null or misaligned pointer, an unknown class, a table whose numbering
+ * or offsets do not fit are argument errors before any launch. */
+/* ref: not in the reference; stands where optimizer.step() does, train.py:2783 */
+long az_adafactor_geometry(int what);
+/* ref: not in the reference; stands where optimizer.step() does, train.py:2783 */
+int az_adafactor_step(int ntensors, const void* desc_host, const void* desc, void* state, long state_numel, void* scratch, long scratch_numel,
+                      void* fac, long fac_numel, void* partials, void* tsc, const void* hyper_host, void* stream);
 
 /* ---- LoRA adapter products (an option the reference does not have -- train.py is full fine-tuning only; INTEGRATION.md "LoRA
  *      (`az_lora_*`)" states the arithmetic, tests/lora_ref.py restates it in float64) -------------------------------------------
